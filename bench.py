@@ -13,6 +13,13 @@ frame / its HIP-event duration on the context's stream.
 cpu_baseline = the oracle (C++ restatement, OpenMP) tracing a bounded band of
 rows of the same frame on this host's cores (rank 0, N=1 only).
 
+A plain run sets up, warms up, times the K steps, writes the last step's outputs
+(--dump-outputs DIR) and prints the result line; the roofline above comes from the
+timed steps' own HIP events.  --full adds what takes work of its own after the
+timed steps: cpu_baseline, roofline_chain_alone, hbm_copy_gbs, primary_hit_frac,
+the committed profiles of the run's mode (roofline.traffic, trace_valu_util,
+trace_roofline) and, on banded runs, band_diag and the band_parity check.
+
 Multi-GPU (N>1, launched by torch.distributed.run): the frame is split into N
 horizontal bands; each rank's library context renders its band and enqueues
 the halo exchanges itself (RCCL over xGMI: grouped send/recv with the band
@@ -225,6 +232,30 @@ def single_context_frames(make, frames, spp, params, primary_only=False):
     return s
 
 
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # --dump-outputs: all arrays together (the files stay under 64 MB)
+DUMP_SEED = 20240611  # the pixel sample of outputs over the limit
+
+
+def dump_outputs(out_dir, arrays):
+    """Write the timed path's last outputs (name -> (H, W[, C]) float array) as out_dir/<name>.npy in
+    float32.  Over DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of pixels
+    (sorted flat pixel indices, also written as sample_pixels.npy), so that two builds run with the same
+    arguments write comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        h, w = next(iter(arrays.values())).shape[:2]
+        per_px = total // (h * w) + 8  # + the pixel's index (float64)
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=DUMP_LIMIT_BYTES // per_px, replace=False))
+        arrays = {k: v.reshape(h * w, -1)[keep] for k, v in arrays.items()}
+        np.save(os.path.join(out_dir, "sample_pixels.npy"), keep.astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k.lower() + ".npy"), v)
+    return sorted(k.lower() for k in arrays)
+
+
 def band_tuning(width, height, world):
     """Schedule defaults of a rank's band (N>1).  A band is latency bound: a third wavefront state
     set lets its passes' first halves run further ahead, and below ~0.7 Mpx a third front stream
@@ -301,8 +332,16 @@ def main():
     ap.add_argument("--bounces", default="3/1",
                     help="total/diffuse bounce limits: 3/1 = the reference's (RayGen.cu:146-147); 4/4 = the "
                          "'4 bounces' of BASELINE.json's config line, labelled as such")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline figure does not need: the "
+                         "CPU baseline, the denoiser chain alone, the copy bandwidth, the committed profiles of this "
+                         "mode, the primary hit fraction; banded runs: the band instrumentation frames and band_parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy (float32; "
+                         "output + depth, --primary-only: depth + normal_rough + albedo; at most 64 MB in all, "
+                         "a fixed seeded pixel sample of larger frames)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--equal-bands", action="store_true",
                     help="N>1: keep the equal row bands instead of balancing the boundaries on measured band times")
     ap.add_argument("--frame-calls", action="store_true",
@@ -311,8 +350,11 @@ def main():
                     help="N=1: run the banded path through a one-rank RCCL communicator (the N>1 schedule, "
                          "its instrumentation and its band_parity check, with no neighbour)")
     ap.add_argument("--no-band-parity", action="store_true",
-                    help="banded runs: skip the check of the gathered frame against a single-context render")
+                    help="banded runs with --full: skip the check of the gathered frame against a single-context "
+                         "render")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     a.bounce_limits = tuple(int(v) for v in a.bounces.split("/"))
     if a.scene is None:
         a.scene = "c1" if a.primary_only else "c3"
@@ -431,11 +473,25 @@ def main():
         elapsed = float(tt.item())
     wd.disarm()
 
+    # --dump-outputs: what the last timed step left in the buffers a caller reads after a frame, before
+    # anything below renders further frames (banded runs: the frame buffer gathered at rank 0)
+    dumped = None
+    if a.dump_outputs:
+        names = ("DEPTH", "NORMAL_ROUGH", "ALBEDO") if a.primary_only else ("OUTPUT", "DEPTH")
+        if banded:
+            names = names[:1]
+        wd.arm(SETUP_LIMIT_S, "output dump")
+        for name in names if banded else ():
+            r.band_gather(name, 0)
+        if rank == 0:
+            dumped = dump_outputs(a.dump_outputs, {name: r.read(name) for name in names})
+        wd.disarm()
+
     # bands: after the timed region, 4 more frames with the library's band instrumentation on
     # (vxpt_band_stats: every frame's trace / denoiser spans, the halo groups' HIP-event time, count and
     # bytes per neighbour) -- what the first multi-GPU run needs to explain its own scaling
     band_diag, timing_src = None, "vxpt_timings (the pipelined run's chains)" if pipelined else "vxpt_timings per frame"
-    if banded and not a.primary_only:
+    if a.full and banded and not a.primary_only:
         wd.frames(4, "band instrumentation frames")
         r.band_stats_enable(True)
         r.render_frames(frame, 4, a.spp, params)
@@ -466,7 +522,7 @@ def main():
     # vxpt_band_gather) against one whole-frame context rendering the same frame sequence on rank 0
     # (tools/rccl_bands_check.py's check, on the benchmarked workload); a mismatch fails the run
     parity = None
-    if banded and not a.no_band_parity:
+    if a.full and banded and not a.no_band_parity:
         name = "DEPTH" if a.primary_only else "OUTPUT"
         wd.frames(frame + 2, "band parity (gather + single-context render of %d frames)" % frame)
         r.band_gather(name, 0)
@@ -507,7 +563,7 @@ def main():
     # profiles/*_pmc_denoise.json) of this same mode only; PMC cannot run inside this timed process
     mode = run_mode(a, 1 if a.primary_only else a.spp)
     traffic, traffic_src, valu, valu_src, trace_roof = None, None, None, None, None
-    if not a.primary_only and not banded:
+    if a.full and not a.primary_only and not banded:
         trace_roof = trace_roofline_profile(mode)
         d, traffic_src = matching_profile("*_pmc_denoise.json", mode)
         traffic = d["traffic_bytes_per_frame"] if d else None
@@ -517,7 +573,7 @@ def main():
     # after the timed region: the same denoiser chain timed over frame-by-frame calls (nothing of the
     # next frame beside or just before it), a labelled extra beside the contract's roofline above
     chain_alone = None
-    if pipelined and not banded:
+    if a.full and pipelined and not banded:
         ds = []
         for _ in range(4):
             r.render_frame(frame, a.spp, params)
@@ -532,28 +588,28 @@ def main():
                                "pass precedes each chain and the chain measures slower"}
     # the box's practical HBM ceiling ("record the measured copy-kernel bandwidth"): a
     # 1 GiB device-to-device copy, read + write bytes / time, best of 5
-    copy_gbs = None
-    try:
-        src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda:%d" % local)
-        dst = torch.empty_like(src)
-        best = None
-        for _ in range(6):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            dst.copy_(src)
-            e1.record()
-            e1.synchronize()
-            ms = e0.elapsed_time(e1)
-            best = ms if best is None else min(best, ms)
-        copy_gbs = round(2 * src.numel() / (best * 1e-3) / 1e9, 1)
-        del src, dst
-    except Exception as e:  # measurement extra only
-        print("copy bandwidth not measured: %s" % e, file=sys.stderr)
-    depth = r.read("DEPTH")
-    hit_frac = float((depth < 1e26).mean())  # scene sanity: fraction of primary rays that hit voxels
-    cpu = None
-    if rank == 0 and not banded and not a.no_cpu_baseline:
-        cpu = cpu_baseline(a, a.cpu_seconds)
+    copy_gbs, hit_frac, cpu = None, None, None
+    if a.full:
+        try:
+            src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda:%d" % local)
+            dst = torch.empty_like(src)
+            best = None
+            for _ in range(6):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                dst.copy_(src)
+                e1.record()
+                e1.synchronize()
+                ms = e0.elapsed_time(e1)
+                best = ms if best is None else min(best, ms)
+            copy_gbs = round(2 * src.numel() / (best * 1e-3) / 1e9, 1)
+            del src, dst
+        except Exception as e:  # measurement extra only
+            print("copy bandwidth not measured: %s" % e, file=sys.stderr)
+        depth = r.read("DEPTH")
+        hit_frac = round(float((depth < 1e26).mean()), 4)  # scene sanity: fraction of primary rays that hit voxels
+        if rank == 0 and not banded and not a.no_cpu_baseline:
+            cpu = cpu_baseline(a, a.cpu_seconds)
     if rank == 0:
         line = {
             "metric": "Mpaths/s @1080p 4spp (+ms/frame, denoiser HBM GB/s vs roofline)",
@@ -584,13 +640,14 @@ def main():
                          "alg_bytes_per_launch": alg_bytes, "avg_duration_ms": round(dur_ms, 4)},
             "trace_ms": round(avg_trace, 4), "denoise_ms": round(avg_dn, 4), "timing_source": timing_src,
             "band_diag": band_diag, "band_parity": parity["band_parity"] if parity else None,
-            "band_parity_detail": parity, "primary_hit_frac": round(hit_frac, 4),
+            "band_parity_detail": parity, "primary_hit_frac": hit_frac,
             # the trace passes over this rank's rows (bands: with their halo exchanges)
             "trace_mpaths_s": round(band_px * spp / (avg_trace * 1e-3) / 1e6, 3),
             "trace_valu_util": valu, "trace_valu_util_source": valu_src, "trace_roofline": trace_roof,
             "roofline_chain_alone": chain_alone,
             "hbm_copy_gbs": copy_gbs,
             "cpu_baseline": cpu,
+            "full": bool(a.full), "dumped_outputs": dumped,
         }
         print(json.dumps(line), flush=True)
     r.close()

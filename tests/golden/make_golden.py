@@ -7,6 +7,8 @@ noise_ref.npz  -- outputs of the reference's OWN terrain noise generator
                   at every column the C1 (2x1x2 chunks, freq 1/64) and C3
                   (8x8x8 chunks, freq 1/256) terrains sample
                   (VoxelSceneGen.cu:361-381), plus the two SURVEY §8c KAT points.
+noise_live_ref.npz -- the same generator at 2000 scattered points with 1, 4 and 6
+                  octaves (test_noise_vs_reference_library_live's points).
 oracle_c1.npz  -- the oracle's own C1 render at 64x48 (regression pin of the
                   restatement itself; NOT reference-derived).
 """
@@ -47,6 +49,26 @@ def make_noise():
     np.savez_compressed(os.path.join(HERE, "noise_ref.npz"), **out)
 
 
+LIVE_OCTAVES = (1, 4, 6)
+
+
+def live_points():
+    """The scattered points of test_noise_vs_reference_library_live."""
+    return np.random.default_rng(5).uniform(-40, 40, size=(2000, 2)).astype(np.float32)
+
+
+def make_noise_live():
+    """noise_live_ref.npz: the same generator at live_points() with 1, 4 and 6 octaves (keys o1, o4, o6)."""
+    lib = ctypes.CDLL(os.path.join(REPO, "oracle", "_ref", "libref_noise.so"))
+    lib.ref_noise.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    xy, out = live_points(), {}
+    for octv in LIVE_OCTAVES:
+        r = np.zeros(len(xy), np.float32)
+        lib.ref_noise(octv, 124, len(xy), xy.ctypes.data, r.ctypes.data)
+        out["o%d" % octv] = r
+    np.savez_compressed(os.path.join(HERE, "noise_live_ref.npz"), **out)
+
+
 def make_oracle_c1():
     import oracle
     o = oracle.Oracle(64, 48)
@@ -71,5 +93,6 @@ def make_oracle_c1():
 
 if __name__ == "__main__":
     make_noise()
+    make_noise_live()
     make_oracle_c1()
     print("wrote", os.listdir(HERE))

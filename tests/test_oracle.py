@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import oracle
-from golden.make_golden import C1_CAMERA, DENOISE_DEFAULT, POINTS, noise_points
+from golden.make_golden import C1_CAMERA, DENOISE_DEFAULT, LIVE_OCTAVES, POINTS, live_points, noise_points
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -46,16 +46,24 @@ def test_noise_map_stats():
 
 
 def test_noise_vs_reference_library_live():
+    """The oracle's noise at 2000 scattered points, 1 / 4 / 6 octaves, bit for bit against the reference
+    generator's recorded outputs (golden/noise_live_ref.npz, make_golden.make_noise_live) -- and, where
+    the reference library itself has been built (oracle/_ref), against its outputs computed now, which
+    must be the recorded ones."""
+    golden = np.load(os.path.join(GOLDEN, "noise_live_ref.npz"))
     path = os.path.join(os.path.dirname(oracle.__file__), "_ref", "libref_noise.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    lib = ctypes.CDLL(path)
-    lib.ref_noise.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    rng = np.random.default_rng(5)
-    xy = rng.uniform(-40, 40, size=(2000, 2)).astype(np.float32)
-    for octv in (1, 4, 6):
-        ref = np.zeros(len(xy), np.float32)
-        lib.ref_noise(octv, 124, len(xy), xy.ctypes.data, ref.ctypes.data)
+    lib = None
+    if os.path.exists(path):
+        lib = ctypes.CDLL(path)
+        lib.ref_noise.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    xy = live_points()
+    for octv in LIVE_OCTAVES:
+        ref = golden["o%d" % octv]
+        assert ref.shape == (len(xy),) and ref.dtype == np.float32
+        if lib is not None:
+            live = np.zeros(len(xy), np.float32)
+            lib.ref_noise(octv, 124, len(xy), xy.ctypes.data, live.ctypes.data)
+            np.testing.assert_array_equal(live.view(np.uint32), ref.view(np.uint32))
         got = np.array([oracle.perlin(float(a), float(b), octv) for a, b in xy], np.float32)
         np.testing.assert_array_equal(got.view(np.uint32), ref.view(np.uint32))
 

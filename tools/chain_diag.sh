@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 for mode in pipe calls; do
     extra=""
     [ $mode = calls ] && extra="--frame-calls"
-    ARGS="--warmup 8 --steps 6 --no-cpu-baseline $extra"
+    ARGS="--full --warmup 8 --steps 6 --no-cpu-baseline $extra"
     timeout -k 10 200 rocprofv3 --kernel-trace -f csv rocpd -d gpurun_out/${TAG}_${mode}_kt -o run -- python bench.py $ARGS > gpurun_out/${TAG}_${mode}_kt.log 2>&1 || { echo "kt $mode failed"; exit 1; }
     timeout -k 10 200 rocprofv3 --pmc GRBM_GUI_ACTIVE TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum -f csv rocpd -d gpurun_out/${TAG}_${mode}_pmc -o run -- python bench.py $ARGS > gpurun_out/${TAG}_${mode}_pmc.log 2>&1 || { echo "pmc $mode failed"; exit 1; }
 done

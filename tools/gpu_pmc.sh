@@ -6,7 +6,7 @@ TAG=${1:-pmc}; shift
 export TMPDIR=/tmp
 cd /tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
-ARGS="--warmup 8 --steps 4 --no-cpu-baseline $*"
+ARGS="--full --warmup 8 --steps 4 --no-cpu-baseline $*"
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE -f csv rocpd -d gpurun_out/${TAG}_cfetch -o run -- ./tools/calib/pmc_calib > gpurun_out/${TAG}_cfetch.log 2>&1 || { echo "calib fetch failed"; exit 1; }
 timeout -k 10 120 rocprofv3 --pmc WRITE_SIZE -f csv rocpd -d gpurun_out/${TAG}_cwrite -o run -- ./tools/calib/pmc_calib > gpurun_out/${TAG}_cwrite.log 2>&1 || { echo "calib write failed"; exit 1; }
 python tools/pmc_calib.py gpurun_out/${TAG}_cfetch/run_results.db gpurun_out/${TAG}_cwrite/run_results.db gpurun_out/${TAG}_pmc_calib.json
