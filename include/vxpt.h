@@ -64,6 +64,8 @@ enum vxpt_buffer {
                                   * the G-buffer planes GetPrevSurface reads (Restir.h:348-381), packed */
     VXPT_BUF_BOX_TABLES = 48,    /* read-only: 8 x nBricks u32, the walk's empty-box extents per brick and ray
                                   * octant (x | y << 8 | z << 16 bricks; 0 = occupied), box_tables.hpp */
+    VXPT_BUF_TEX_BLOCKS = 50,    /* read-only: the raw block bytes of a block-compressed texture set
+                                  * (vxpt_load_textures_bc without VXPT_TEX_EXPAND; vxpt_texture_table_bc) */
     VXPT_BUF_CLAMP_DECISION = 49 /* read-only parity hook (vxpt_debug_clamp_decisions): per pixel, a float
                                   * holding the last denoise's history-clamp decision bits -- 1: the x-only
                                   * Float3 compare cmin.x < centre.x (HistoryClamping.h:124), 2: cmax.x >
@@ -234,13 +236,51 @@ int vxpt_set_camera_angles(vxpt_ctx *ctx, const float pos[3], float yaw, float p
 
 /* ---- textures (TextureManager.cu:133-330; shading closesthit.cu:167-254) ---- */
 /* load every texture the cube materials name (paths from assets/materials.yaml, relative to root;
- * NULL = data_dir) as RGBA8 mip chains and turn textured shading on; missing or non-square files
+ * NULL = data_dir) as RGBA8 mip chains and turn textured shading on (the default texel storage;
+ * vxpt_load_textures_bc below keeps the reference's block-compressed formats); missing or non-square files
  * are skipped (their materials stay untextured).  *loaded = textures loaded */
 int vxpt_load_textures(vxpt_ctx *ctx, const char *root, int *loaded);
 /* textured shading on/off once loaded (the untextured parity scenes use off) */
 int vxpt_enable_textures(vxpt_ctx *ctx, int on);
 /* texture table: per texture size, maxLod, maxLod + 1 level offsets in texels (parity hook) */
 int vxpt_texture_table(vxpt_ctx *ctx, int32_t *out, int cap, int *n_textures, int64_t *n_texels);
+
+/* ---- block-compressed textures (TextureManager.cu:189-330) ----
+ * The reference keeps every texture as BC7 (3 / 4 channels), BC5 (2) or BC4 (1) mip chains
+ * (:193-210), caches the compressed levels as raw block files (:271-287) and samples them through
+ * the texture unit.  Here the sampler decodes the texel's 4x4 block itself (csrc/bcn_decode.hpp);
+ * the decode of a block is fully specified, so given the reference's block bytes the texels are
+ * the reference's.  BC4 / BC5 interpolants are 8-bit (truncating division): DESIGN §7. */
+enum vxpt_bc_format { VXPT_BC4 = 4, VXPT_BC5 = 5, VXPT_BC7 = 7 };
+enum vxpt_texture_flags {
+    VXPT_TEX_WRITE_CACHE = 1, /* write the levels this call encodes to cache_dir */
+    VXPT_TEX_EXPAND = 2       /* decode the blocks on the host into the RGBA8 texel buffer: the block
+                               * set's exact texels through the RGBA8 sampler, at 4x the bytes */
+};
+/* vxpt_load_textures with every level stored as blocks: the same texture set, sorted-path ids,
+ * material binding and mip chain; the format follows the PNG's channel count (:193-210).  A level
+ * whose cache file <cache_dir>/<name>_lod_<l>.bin (<name>: the material's path after its first '/'
+ * up to ".png", :168-173) holds exactly size^2 / 16 blocks -- rows of blocks top-down, pitch
+ * size / 4 x bytes per block (:271-287) -- takes the file's bytes verbatim; a file of any other
+ * size is ignored and the level is encoded (vxpt_bc_encode).  cache_dir may be NULL.
+ * *levels_from_cache = levels taken from files.  Replaces any texture set loaded before. */
+int vxpt_load_textures_bc(vxpt_ctx *ctx, const char *root, const char *cache_dir, int flags, int *loaded,
+                          int *levels_from_cache);
+/* block table: per texture format, size, maxLod, then maxLod + 1 level offsets in bytes into
+ * VXPT_BUF_TEX_BLOCKS (every chain padded so that each level starts 16-byte aligned) */
+int vxpt_texture_table_bc(vxpt_ctx *ctx, int64_t *out, int cap, int *n_textures, int64_t *n_bytes);
+/* host codec, no context needed.  decode: n_blocks_x x n_blocks_y blocks (rows top-down) -> RGBA8
+ * rows of 4 n_blocks_x texels; BC4 -> (v, 0, 0, 255), BC5 -> (v, a, 0, 255).  The body the sampler runs. */
+int vxpt_bc_decode(int format, const void *blocks, int n_blocks_x, int n_blocks_y, uint8_t *rgba_out);
+/* encode: w x h RGBA8 texels (multiples of 4) -> blocks.  Deterministic (integer arithmetic): BC7
+ * mode 6 with endpoints on the block's colour-box diagonal, BC4 / BC5 max / min endpoints in the
+ * 8-value mode.  It does not try to match the reference's encoder (NVTT). */
+int vxpt_bc_encode(int format, const uint8_t *rgba, int w, int h, void *blocks_out);
+/* the cache file of one level (TextureManager.cu:168-173, 271) */
+int vxpt_bc_cache_path(const char *cache_dir, const char *tex_path, int lod, char *out, int cap);
+/* one size x size level as the loader resolves it: cache file or encode (flags: VXPT_TEX_WRITE_CACHE) */
+int vxpt_bc_level(int format, const uint8_t *rgba, int size, const char *cache_dir, const char *tex_path, int lod,
+                  int flags, void *blocks_out, int *from_cache);
 
 /* ---- instanced block meshes + emissive triangle lights ---- */
 /* BlockManager / ModelManager / VoxelEngine::{collectInstanceTransforms, generateInstanceLights}
@@ -491,6 +531,9 @@ int vxpt_probe_rays(vxpt_ctx *ctx, int n, const float *rays, int32_t *out6, floa
 /* blue-noise sampler probe: n queries (pixel x, pixel y, iterationIndex, dimension) ->
  * BlueNoiseRandGenerator::rand (RandGen.h:21-45) as the trace kernel evaluates it */
 int vxpt_probe_rng(vxpt_ctx *ctx, int n, const int32_t *q4, float *out);
+/* texture sampler probe: n (u, v, lod) triples -> n x RGBA, tex2DLod of texture tex_id as the trace
+ * kernel evaluates it, on whichever texture set the context holds (RGBA8 or blocks) */
+int vxpt_probe_texture(vxpt_ctx *ctx, int tex_id, int n, const float *uvlod, float *out);
 /* ray-queue counters of the last trace pass (no reference counterpart: the wavefront's
  * own instrumentation, read after the pass): for each of the 16 queues q (4*segment + kind,
  * kind 1 BRDF-candidate closest-hit rays, 2 NEE visibility rays, 3 ReSTIR visibility rays)

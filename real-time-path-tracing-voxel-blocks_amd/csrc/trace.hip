@@ -40,6 +40,9 @@
 #ifndef VX_WPE_SHADE
 #define VX_WPE_SHADE 5
 #endif
+#ifndef VX_WPE_SHADE_BC  // k_shade_bc<false>: the block decode spills 92 B/lane at 5 waves (96 VGPRs), none at 4
+#define VX_WPE_SHADE_BC 4
+#endif
 #ifndef VX_WPE_NEE
 #define VX_WPE_NEE 1
 #endif
@@ -821,8 +824,9 @@ VX_D void light_ray(const LSample &ls, V3 p, float extra, V3 &dir, float &tmax) 
     tmax = ls.type == LtLocal ? length(ls.position - p) - 0.01f - extra : kRayMax;
 }
 
-// closesthit / miss for the segment's ray; candidate generation for NEE
-template <bool MESH>
+// closesthit / miss for the segment's ray; candidate generation for NEE.  BC: the loaded texture set is
+// block-compressed (a property of the launch: k_shade_bc)
+template <bool MESH, bool BC = false>
 VX_D void shade_slot(const TraceArgs &a, int seg, int s, QRays &qr) {
     int px, py;
     if (!slot_pixel(a, s, px, py)) return;
@@ -896,9 +900,14 @@ VX_D void shade_slot(const TraceArgs &a, int seg, int s, QRays &qr) {
         if (seg > 0) w.pRad[s].w = travelled;
         sf.albedo = V3(m.albedo[0], m.albedo[1], m.albedo[2]);
         sf.roughness = m.roughness;
-        apply_textures(a.texels, a.tex, m, texPos, ng, wo, ray_cone_spread(a.cam, px, py) * travelled, sf.albedo,
-                       sf.roughness, sf.metallic, sf.normal, MESH && g.mesh,
-                       (MESH && g.mesh) ? mesh_tc(a, h, g.u, g.v) : V2(0.0f, 0.0f));
+        if constexpr (BC)
+            apply_textures(BcSet{a.texBlocks, a.tex, a.texBc}, m, texPos, ng, wo,
+                           ray_cone_spread(a.cam, px, py) * travelled, sf.albedo, sf.roughness, sf.metallic, sf.normal,
+                           MESH && g.mesh, (MESH && g.mesh) ? mesh_tc(a, h, g.u, g.v) : V2(0.0f, 0.0f));
+        else
+            apply_textures(Rgba8Set{a.texels, a.tex}, m, texPos, ng, wo, ray_cone_spread(a.cam, px, py) * travelled,
+                           sf.albedo, sf.roughness, sf.metallic, sf.normal, MESH && g.mesh,
+                           (MESH && g.mesh) ? mesh_tc(a, h, g.u, g.v) : V2(0.0f, 0.0f));
     } else {
         sf.albedo = max3(V3(m.albedo[0], m.albedo[1], m.albedo[2]), V3(0.001f));
         sf.roughness = m.roughness;
@@ -1051,6 +1060,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MESH ? 3 : 
     QRays qr;
     qr.mask = 0u;
     shade_slot<MESH>(a, seg, blockIdx.x * 256 + threadIdx.x, qr);
+    block_enqueue(a, 4 * seg + 1, qr);
+}
+
+// k_shade over a block-compressed texture set (TraceArgs::texBlocks): the same body, its sampler
+// decoding the texel's block
+template <bool MESH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MESH ? 3 : VX_WPE_SHADE_BC))) void k_shade_bc(TraceArgs a, int seg) {
+    QRays qr;
+    qr.mask = 0u;
+    shade_slot<MESH, true>(a, seg, blockIdx.x * 256 + threadIdx.x, qr);
     block_enqueue(a, 4 * seg + 1, qr);
 }
 
@@ -1638,6 +1657,15 @@ __global__ __launch_bounds__(256) void k_probe_rng(BlueNoiseDev bn, int n, const
 }
 
 // rebuilds a slot's tap records from its planes (after a host write to the planes)
+// vxpt_probe_texture: tex_lod as apply_textures calls it
+template <class Set>
+__global__ __launch_bounds__(256) void k_probe_texture(Set set, int id, int n, const float *uvlod, float4 *out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const V4 c = tex_lod(set[id], uvlod[3 * i], uvlod[3 * i + 1], uvlod[3 * i + 2]);
+    out[i] = make_float4(c.x, c.y, c.z, c.w);
+}
+
 __global__ __launch_bounds__(256) void k_pack_rec(GBuf g, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -1668,6 +1696,14 @@ hipError_t launch_pack_rec(const GBuf &g, size_t n, hipStream_t st) {
 
 hipError_t launch_probe_rng(const BlueNoiseDev &bn, int n, const int *q, float *out, hipStream_t st) {
     hipLaunchKernelGGL(k_probe_rng, dim3((n + 255) / 256), dim3(256), 0, st, bn, n, q, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_probe_texture(const TexInfo *tex, const uchar4 *texels, const TexBcInfo *texBc, const uint8_t *blocks,
+                                int id, int n, const float *uvlod, float4 *out, hipStream_t st) {
+    const dim3 g((n + 255) / 256), b(256);
+    if (blocks) hipLaunchKernelGGL(k_probe_texture<BcSet>, g, b, 0, st, BcSet{blocks, tex, texBc}, id, n, uvlod, out);
+    else hipLaunchKernelGGL(k_probe_texture<Rgba8Set>, g, b, 0, st, Rgba8Set{texels, tex}, id, n, uvlod, out);
     return hipGetLastError();
 }
 
@@ -1741,7 +1777,10 @@ struct Launcher {
     // a segment's shading up to its NEE visibility rays (the shading kernels' mesh variants -- mesh hits,
     // thin films, local lights -- run only with meshes)
     void first_half(int seg) {
-        if (mesh) hipLaunchKernelGGL(k_shade<true>, g, b, 0, st, a, seg);
+        if (a.texBlocks) {
+            if (mesh) hipLaunchKernelGGL(k_shade_bc<true>, g, b, 0, st, a, seg);
+            else hipLaunchKernelGGL(k_shade_bc<false>, g, b, 0, st, a, seg);
+        } else if (mesh) hipLaunchKernelGGL(k_shade<true>, g, b, 0, st, a, seg);
         else hipLaunchKernelGGL(k_shade<false>, g, b, 0, st, a, seg);
         trav(false, 4 * seg + 1, a.nSlots);
         if (mesh) hipLaunchKernelGGL(k_nee<true>, g, b, 0, st, a, seg);

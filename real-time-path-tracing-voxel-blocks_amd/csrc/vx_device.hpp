@@ -4,6 +4,7 @@
 #pragma once
 #include <climits>
 #include "vx_mesh.hpp"
+#include "bcn_decode.hpp"
 
 namespace vx {
 namespace {
@@ -958,38 +959,80 @@ VX_D V3 sky_emission(const SkyDev &k, V3 dir) {  // miss.cu:53-77
 }
 
 // ---------------------------------------------------------------- textures
-// tex2DLod on an RGBA8 mip chain (TextureManager.cu:228-246: wrap addressing, linear filter,
-// linear mip filter, normalized coordinates, unorm reads, lod clamped to [0, maxLod]).  The
-// hardware's 8-bit fixed-point filter weights are float weights here (the oracle does the same).
+// tex2DLod on a mip chain (TextureManager.cu:228-246: wrap addressing, linear filter, linear mip
+// filter, normalized coordinates, unorm reads, lod clamped to [0, maxLod]).  The hardware's 8-bit
+// fixed-point filter weights are float weights here (the oracle does the same).  The filter is one
+// body over a texture view T: T::ti (size, maxLod) and T::fetch(level, level size, x, y) -> the
+// texel's channels / 255.  Rgba8Tex reads the RGBA8 texel buffer, BcTex decodes the texel's block.
 VX_D float4 texel_f(const uchar4 *t, unsigned off, int S, int x, int y) {
     const uchar4 v = t[off + (unsigned)(y * S + x)];
     return make_float4(v.x / 255.0f, v.y / 255.0f, v.z / 255.0f, v.w / 255.0f);
 }
+// The texel of a block-compressed level (TexBcInfo): one aligned 16-byte load of its 4x4 block (BC7,
+// BC5) or one 8-byte load (BC4), decoded by the body the host decodes with (bcn_decode.hpp)
+VX_D float4 texel_bc(const uint8_t *blocks, int format, unsigned off, int S, int x, int y) {
+    const unsigned bi = (unsigned)((y >> 2) * (S >> 2) + (x >> 2));
+    const int t = (x & 3) + 4 * (y & 3);
+    bcn::Block128 b;
+    if (format == bcn::kBc4) {
+        const uint2 q = *reinterpret_cast<const uint2 *>(blocks + off + (size_t)bi * 8);
+        b.w[0] = q.x; b.w[1] = q.y; b.w[2] = 0u; b.w[3] = 0u;
+    } else {
+        const uint4 q = *reinterpret_cast<const uint4 *>(blocks + off + (size_t)bi * 16);
+        b.w[0] = q.x; b.w[1] = q.y; b.w[2] = q.z; b.w[3] = q.w;
+    }
+    const bcn::Rgba v = bcn::texel(format, b, t);
+    return make_float4(v.r / 255.0f, v.g / 255.0f, v.b / 255.0f, v.a / 255.0f);
+}
+struct Rgba8Tex {
+    const uchar4 *t;
+    const TexInfo &ti;
+    VX_D float4 fetch(int l, int S, int x, int y) const { return texel_f(t, ti.off[l], S, x, y); }
+};
+struct BcTex {
+    const uint8_t *blocks;
+    const TexInfo &ti;
+    const TexBcInfo &bi;
+    VX_D float4 fetch(int l, int S, int x, int y) const { return texel_bc(blocks, bi.format, bi.off[l], S, x, y); }
+};
+// a loaded texture set: set[id] = the view of texture id
+struct Rgba8Set {
+    const uchar4 *texels;
+    const TexInfo *tex;
+    VX_D Rgba8Tex operator[](int id) const { return Rgba8Tex{texels, tex[id]}; }
+};
+struct BcSet {
+    const uint8_t *blocks;
+    const TexInfo *tex;
+    const TexBcInfo *bc;
+    VX_D BcTex operator[](int id) const { return BcTex{blocks, tex[id], bc[id]}; }
+};
 VX_D int wrap_i(int i, int S) {
     const int m = i % S;
     return m < 0 ? m + S : m;
 }
-VX_D V4 tex_bilinear(const uchar4 *t, const TexInfo &ti, int l, float u, float v) {
-    const int S = ti.size >> l;
+template <class T>
+VX_D V4 tex_bilinear(const T &tx, int l, float u, float v) {
+    const int S = tx.ti.size >> l;
     const float x = u * (float)S - 0.5f, y = v * (float)S - 0.5f;
     const float fx = floorf(x), fy = floorf(y);
     const float ax = x - fx, ay = y - fy;
     const int x0 = wrap_i((int)fx, S), x1 = wrap_i((int)fx + 1, S);
     const int y0 = wrap_i((int)fy, S), y1 = wrap_i((int)fy + 1, S);
-    const unsigned o = ti.off[l];
-    const float4 a = texel_f(t, o, S, x0, y0), b = texel_f(t, o, S, x1, y0);
-    const float4 c = texel_f(t, o, S, x0, y1), d = texel_f(t, o, S, x1, y1);
+    const float4 a = tx.fetch(l, S, x0, y0), b = tx.fetch(l, S, x1, y0);
+    const float4 c = tx.fetch(l, S, x0, y1), d = tx.fetch(l, S, x1, y1);
     const float w00 = (1.0f - ax) * (1.0f - ay), w10 = ax * (1.0f - ay), w01 = (1.0f - ax) * ay, w11 = ax * ay;
     return V4(a.x * w00 + b.x * w10 + c.x * w01 + d.x * w11, a.y * w00 + b.y * w10 + c.y * w01 + d.y * w11,
               a.z * w00 + b.z * w10 + c.z * w01 + d.z * w11, a.w * w00 + b.w * w10 + c.w * w01 + d.w * w11);
 }
-VX_D V4 tex_lod(const uchar4 *t, const TexInfo &ti, float u, float v, float lod) {
-    lod = fminf(fmaxf(lod, 0.0f), (float)ti.maxLod);
+template <class T>
+VX_D V4 tex_lod(const T &tx, float u, float v, float lod) {
+    lod = fminf(fmaxf(lod, 0.0f), (float)tx.ti.maxLod);
     const int l0 = (int)floorf(lod);
     const float fl = lod - (float)l0;
-    const V4 c0 = tex_bilinear(t, ti, l0, u, v);
+    const V4 c0 = tex_bilinear(tx, l0, u, v);
     if (!(fl > 0.0f)) return c0;
-    const V4 c1 = tex_bilinear(t, ti, min(l0 + 1, ti.maxLod), u, v);
+    const V4 c1 = tex_bilinear(tx, min(l0 + 1, tx.ti.maxLod), u, v);
     return c0 * (1.0f - fl) + c1 * fl;
 }
 
@@ -1006,7 +1049,9 @@ VX_D float ray_cone_spread(const CamDev &cam, int px, int py) {
 // lod, albedo x texture, roughness / metallic from textures, tangent-space normal map aligned to
 // the face and blended at strength 0.2.  coneWidth = the ray cone's width at this hit.
 // vertexTc: the mesh triangle's interpolated texcoords (closesthit.cu:189; useVertexTc = a mesh hit)
-VX_D void apply_textures(const uchar4 *texels, const TexInfo *tex, const MatDev &m, V3 pos, V3 ng, V3 wo,
+// set: the loaded texture set (Rgba8Set or BcSet)
+template <class Set>
+VX_D void apply_textures(const Set &set, const MatDev &m, V3 pos, V3 ng, V3 wo,
                          float coneWidth, V3 &albedo, float &roughness, bool &metallic, V3 &normal,
                          bool useVertexTc = false, V2 vertexTc = V2(0.0f, 0.0f)) {
     V2 tc(0.0f, 0.0f);
@@ -1021,14 +1066,14 @@ VX_D void apply_textures(const uchar4 *texels, const TexInfo *tex, const MatDev 
     const float mip0 = sqrtf(1024.0f * 1024.0f + 1024.0f * 1024.0f);  // MaterialParameter::texSize (1024, 1024)
     const float lod = log2f(coneWidth / fmaxf(dot(ng, wo), 0.2f) / m.uvScale * 2.0f * mip0) - 3.0f;
     if (m.tex[0] >= 0) {
-        const V4 c = tex_lod(texels, tex[m.tex[0]], tc.x, tc.y, lod);
+        const V4 c = tex_lod(set[m.tex[0]], tc.x, tc.y, lod);
         albedo = albedo * V3(c.x, c.y, c.z);
     }
     albedo = max3(albedo, V3(0.001f));
-    if (m.tex[2] >= 0) roughness = tex_lod(texels, tex[m.tex[2]], tc.x, tc.y, lod).x;
-    if (m.tex[3] >= 0) metallic = tex_lod(texels, tex[m.tex[3]], tc.x, tc.y, lod).x > 0.5f;
+    if (m.tex[2] >= 0) roughness = tex_lod(set[m.tex[2]], tc.x, tc.y, lod).x;
+    if (m.tex[3] >= 0) metallic = tex_lod(set[m.tex[3]], tc.x, tc.y, lod).x > 0.5f;
     if (m.tex[1] >= 0) {
-        const V4 c = tex_lod(texels, tex[m.tex[1]], tc.x, tc.y, lod);
+        const V4 c = tex_lod(set[m.tex[1]], tc.x, tc.y, lod);
         V3 n = normalize(V3(c.x - 0.5f, c.y - 0.5f, c.z - 0.5f));
         n.x = -n.x;
         n.y = -n.y;

@@ -41,6 +41,14 @@ struct TexInfo {
     unsigned off[kMaxTexLevels];
 };
 
+// A block-compressed texture set keeps TexInfo (size, maxLod) and adds this table: the texture's
+// format (bcn_decode.hpp: 4, 5, 7) and off[l] = the byte offset of level l's first block in the
+// block buffer, 16-byte aligned; blocks row-major, (size >> l) / 4 per row
+struct TexBcInfo {
+    int format;
+    unsigned off[kMaxTexLevels];
+};
+
 struct AliasBin { float q, p; int alias; };
 
 struct Reservoir { uint32_t lightData, uvData; float weightSum, targetPdf, M; };
@@ -244,6 +252,10 @@ struct TraceArgs {
     int writeMotion;    // store the (zero) motion vectors: the plane may hold a host upload
     int writePlanes;    // store the G-buffer planes (0: a frame's passes before its last -- only their tap
                         // records are read, by the next pass's temporal reuse)
+    // block-compressed texture set (vxpt_load_textures_bc): non-null texBlocks selects the kernels whose
+    // sampler decodes blocks (tex still holds size / maxLod; texels is then unused)
+    const TexBcInfo *texBc;
+    const uint8_t *texBlocks;
 };
 
 // kernel launchers (defined in the .hip translation units)
@@ -259,6 +271,9 @@ hipError_t launch_trace_back(const TraceArgs &a, hipStream_t st, hipEvent_t wait
 // GBuf::rec of the n pixels from the planes
 hipError_t launch_pack_rec(const GBuf &g, size_t n, hipStream_t st);
 hipError_t launch_probe_rng(const BlueNoiseDev &bn, int n, const int *q, float *out, hipStream_t st);
+// tex_lod of texture id for n (u, v, lod) triples -> n float4; blocks non-null: the block sampler
+hipError_t launch_probe_texture(const TexInfo *tex, const uchar4 *texels, const TexBcInfo *texBc, const uint8_t *blocks,
+                                int id, int n, const float *uvlod, float4 *out, hipStream_t st);
 
 struct DenoiseParamsDev {
     float maxAcc, maxFast, phiL, lobeAngleFraction, roughnessFraction, depthThreshold;

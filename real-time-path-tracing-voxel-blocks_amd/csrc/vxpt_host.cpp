@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/vxpt.h"
+#include "bcn.hpp"
 #include "box_tables.hpp"
 #include "bvh_build.hpp"
 #include "light_map.hpp"
@@ -265,6 +266,13 @@ struct vxpt_ctx {
     std::vector<TexInfo> hTex;
     size_t nTexels = 0;
     int texEnabled = 0;
+    // block-compressed texture set (vxpt_load_textures_bc): hTexBc is filled for every such load, the
+    // device buffers only when the sampler decodes blocks (texBcOn; not with VXPT_TEX_EXPAND)
+    DBuf<uint8_t> texBlocks;
+    DBuf<TexBcInfo> texBcTable;
+    std::vector<TexBcInfo> hTexBc;
+    size_t nTexBlockBytes = 0;
+    bool texBcOn = false;
 
     // instanced block meshes and their emissive-triangle lights
     struct BlockDef {
@@ -684,7 +692,9 @@ bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, 
         case VXPT_BUF_CELL_MASKS: p = c->cellMask.p; bytes = (size_t)c->nBricks * 8; return !forWrite && c->cellMask.p;
         case VXPT_BUF_BRICK_IDS: p = c->bricks.p; bytes = (size_t)c->nBricks * 64; return !forWrite && c->bricks.p;
         case VXPT_BUF_MACRO_MASKS: p = c->macro.p; bytes = (size_t)c->nBricks / 64 * 8; return !forWrite && c->macro.p;
-        case VXPT_BUF_TEXELS: p = c->texels.p; bytes = c->nTexels * 4; return !forWrite && c->texels.p;
+        case VXPT_BUF_TEXELS: p = c->texels.p; bytes = c->nTexels * 4; return !forWrite && c->texels.p && !c->texBcOn;
+        case VXPT_BUF_TEX_BLOCKS:
+            p = c->texBlocks.p; bytes = c->nTexBlockBytes; return !forWrite && c->texBcOn && c->texBlocks.p;
         case VXPT_BUF_BLOOM: p = c->bloomB; bytes = n * 16; return c->bloomB != nullptr;
         case VXPT_BUF_LIGHTS: p = c->lights.p; bytes = (size_t)c->nLights * sizeof(LightInfo); return !forWrite && c->nLights;
         case VXPT_BUF_TAP_RECORD: p = g.rec; bytes = n * 32; return !forWrite;
@@ -1041,6 +1051,8 @@ int trace_front(vxpt_ctx *c, int32_t it, uint32_t flags, bool accumulate, bool a
     a.tex = c->texTable.p;
     a.texels = c->texels.p;
     a.texEnabled = (c->texEnabled && c->texTable.p) ? 1 : 0;
+    a.texBc = c->texBcOn ? c->texBcTable.p : nullptr;
+    a.texBlocks = c->texBcOn ? c->texBlocks.p : nullptr;
     c->prevSceneEmpty = 0;
     if (a.primaryOnly) {
         HIPCHK(c, launch_trace_front(a, c->stream));
@@ -2207,24 +2219,22 @@ int vxpt_set_camera(vxpt_ctx *c, const vxpt_camera *cur, const vxpt_camera *prev
     return VXPT_OK;
 }
 
+namespace {
+
 // TextureManager::initWithMaterialPaths + LoadTexturesFromPaths (TextureManager.cu:133-330):
 // every texture the cube materials name, in sorted path order (= texture id); decoded, square
 // power-of-two, expanded to RGBA8 (1 channel -> (v,0,0,1), 2 -> (v,a,0,1), 3 -> (r,g,b,1): the
 // unorm reads of the BC4/BC5/BC7 formats), levels 0..log2(size)-2 by 2x2 box averages truncated
-// to 8 bits (fillMipmapKernel, :82-117, and its CPU twin, :390-414).  BC7 itself is not
-// reproduced (NVTT): the texels are the uncompressed ones.
-int vxpt_load_textures(vxpt_ctx *c, const char *root, int *loaded) {
-    if (!c) return VXPT_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->dev));
-    const std::string base = root ? root : c->dataDir;
+// to 8 bits (fillMipmapKernel, :82-117, and its CPU twin, :390-414).  Binds mats[].tex[].
+// paths / channels (optional): each loaded texture's material path and PNG channel count.
+void build_mip_chains(vxpt_ctx *c, const std::string &base, std::vector<uchar4> &texels, std::vector<TexInfo> &table,
+                      std::vector<std::string> *texPaths, std::vector<int> *channels) {
     std::vector<std::string> paths;
     for (int b = 1; b <= 12; ++b)
         for (int k = 0; k < 4; ++k)
             if (!c->texPath[b][k].empty()) paths.push_back(c->texPath[b][k]);
     std::sort(paths.begin(), paths.end());
     paths.erase(std::unique(paths.begin(), paths.end()), paths.end());
-    std::vector<uchar4> texels;
-    std::vector<TexInfo> table;
     std::map<std::string, int> idOf;
     for (const std::string &pth : paths) {
         int w, h, ch;
@@ -2262,14 +2272,32 @@ int vxpt_load_textures(vxpt_ctx *c, const char *root, int *loaded) {
         }
         idOf[pth] = (int)table.size();
         table.push_back(ti);
+        if (texPaths) texPaths->push_back(pth);
+        if (channels) channels->push_back(ch);
     }
     for (int b = 1; b <= 12; ++b)
         for (int k = 0; k < 4; ++k) {
             const auto it = idOf.find(c->texPath[b][k]);
             c->mats[b].tex[k] = it == idOf.end() ? -1 : it->second;
         }
+}
+
+}  // namespace
+
+// The RGBA8 texture set (the default): build_mip_chains' texels as they are, sampled by texel_f.
+// The reference's block-compressed storage of the same chains is vxpt_load_textures_bc.
+int vxpt_load_textures(vxpt_ctx *c, const char *root, int *loaded) {
+    if (!c) return VXPT_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->dev));
+    const std::string base = root ? root : c->dataDir;
+    std::vector<uchar4> texels;
+    std::vector<TexInfo> table;
+    build_mip_chains(c, base, texels, table, nullptr, nullptr);
     c->hTex = table;
     c->nTexels = texels.size();
+    c->hTexBc.clear();
+    c->nTexBlockBytes = 0;
+    c->texBcOn = false;
     if (!table.empty()) {
         if (int r = upload_vec(c, c->texels, texels.data(), texels.size())) return r;
         if (int r = upload_vec(c, c->texTable, table.data(), table.size())) return r;
@@ -2277,6 +2305,62 @@ int vxpt_load_textures(vxpt_ctx *c, const char *root, int *loaded) {
     }
     c->texEnabled = table.empty() ? 0 : 1;
     if (loaded) *loaded = (int)table.size();
+    return VXPT_OK;
+}
+
+// The same set with every level as BC7 / BC5 / BC4 blocks (TextureManager.cu:189-330): the format
+// from the PNG's channel count (:193-210), each level's blocks from its cache file or the encoder
+// (bcn.hpp level_blocks; :271-287), every chain padded to 16 bytes so that BC7 / BC5 levels start
+// aligned (a BC4 level is a multiple of 8).  VXPT_TEX_EXPAND decodes the blocks back into the
+// RGBA8 buffer (same offsets as vxpt_load_textures) and samples that.
+int vxpt_load_textures_bc(vxpt_ctx *c, const char *root, const char *cache_dir, int flags, int *loaded,
+                          int *levels_from_cache) {
+    if (!c) return VXPT_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->dev));
+    const std::string base = root ? root : c->dataDir;
+    std::vector<uchar4> texels;
+    std::vector<TexInfo> table;
+    std::vector<std::string> texPaths;
+    std::vector<int> channels;
+    build_mip_chains(c, base, texels, table, &texPaths, &channels);
+    std::vector<uint8_t> blocks, level;
+    std::vector<TexBcInfo> bcTable;
+    int cached = 0;
+    const bool expand = (flags & VXPT_TEX_EXPAND) != 0;
+    for (size_t i = 0; i < table.size(); ++i) {
+        TexBcInfo bi{};
+        bi.format = bcn::format_of_channels(channels[i]);
+        for (int l = 0; l <= table[i].maxLod; ++l) {
+            const int S = table[i].size >> l;
+            uint8_t *rgba = reinterpret_cast<uint8_t *>(texels.data() + table[i].off[l]);
+            cached += bcn::level_blocks(bi.format, rgba, S, cache_dir ? cache_dir : "", texPaths[i], l,
+                                        (flags & VXPT_TEX_WRITE_CACHE) != 0, level) ? 1 : 0;
+            if (blocks.size() + level.size() > 0xfffffff0ull) return fail(c, VXPT_ERR_ARG, "texture blocks exceed 4 GiB");
+            bi.off[l] = (unsigned)blocks.size();
+            blocks.insert(blocks.end(), level.begin(), level.end());
+            if (expand) bcn::decode(bi.format, level.data(), S / 4, S / 4, rgba);
+        }
+        blocks.resize((blocks.size() + 15) & ~(size_t)15);
+        bcTable.push_back(bi);
+    }
+    c->hTex = table;
+    c->nTexels = texels.size();
+    c->hTexBc = bcTable;
+    c->nTexBlockBytes = blocks.size();
+    c->texBcOn = !expand && !table.empty();
+    if (!table.empty()) {
+        if (expand) {
+            if (int r = upload_vec(c, c->texels, texels.data(), texels.size())) return r;
+        } else {
+            if (int r = upload_vec(c, c->texBlocks, blocks.data(), blocks.size())) return r;
+            if (int r = upload_vec(c, c->texBcTable, bcTable.data(), bcTable.size())) return r;
+        }
+        if (int r = upload_vec(c, c->texTable, table.data(), table.size())) return r;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->texEnabled = table.empty() ? 0 : 1;
+    if (loaded) *loaded = (int)table.size();
+    if (levels_from_cache) *levels_from_cache = cached;
     return VXPT_OK;
 }
 
@@ -2704,6 +2788,26 @@ int vxpt_texture_table(vxpt_ctx *c, int32_t *out, int cap, int *n_textures, int6
     }
     if (n_textures) *n_textures = (int)c->hTex.size();
     if (n_texels) *n_texels = (int64_t)c->nTexels;
+    return VXPT_OK;
+}
+
+// the block table: per texture format, size, maxLod, then maxLod + 1 level offsets (in bytes)
+int vxpt_texture_table_bc(vxpt_ctx *c, int64_t *out, int cap, int *n_textures, int64_t *n_bytes) {
+    if (!c) return VXPT_ERR_ARG;
+    int k = 0;
+    for (size_t i = 0; i < c->hTexBc.size(); ++i) {
+        const TexInfo &t = c->hTex[i];
+        if (out && k + 3 + t.maxLod + 1 > cap) return VXPT_ERR_ARG;
+        if (out) {
+            out[k] = c->hTexBc[i].format;
+            out[k + 1] = t.size;
+            out[k + 2] = t.maxLod;
+            for (int l = 0; l <= t.maxLod; ++l) out[k + 3 + l] = (int64_t)c->hTexBc[i].off[l];
+        }
+        k += 3 + t.maxLod + 1;
+    }
+    if (n_textures) *n_textures = (int)c->hTexBc.size();
+    if (n_bytes) *n_bytes = (int64_t)c->nTexBlockBytes;
     return VXPT_OK;
 }
 
@@ -3751,6 +3855,24 @@ extern "C" int vxpt_probe_rng(vxpt_ctx *c, int n, const int32_t *q4, float *out)
     HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     hipFree(dq);
+    hipFree(dout);
+    return VXPT_OK;
+}
+
+extern "C" int vxpt_probe_texture(vxpt_ctx *c, int tex_id, int n, const float *uvlod, float *out) {
+    if (!c || n <= 0 || !uvlod || !out) return VXPT_ERR_ARG;
+    if (tex_id < 0 || tex_id >= (int)c->hTex.size()) return fail(c, VXPT_ERR_ARG, "no such texture");
+    HIPCHK(c, hipSetDevice(c->dev));
+    float *din;
+    float4 *dout;
+    HIPCHK(c, hipMalloc(&din, (size_t)n * 12));
+    HIPCHK(c, hipMalloc(&dout, (size_t)n * 16));
+    HIPCHK(c, hipMemcpyAsync(din, uvlod, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_probe_texture(c->texTable.p, c->texels.p, c->texBcOn ? c->texBcTable.p : nullptr,
+                                   c->texBcOn ? c->texBlocks.p : nullptr, tex_id, n, din, dout, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(din);
     hipFree(dout);
     return VXPT_OK;
 }

@@ -53,6 +53,9 @@ struct Options {
     std::string perfReport;
     bool testSequence = false, removal20 = false, removalCircle = false;
     bool textures = true;
+    // block-compressed textures (vxpt_load_textures_bc): blocks decoded in the sampler, or expanded to RGBA8
+    bool bcTextures = false, expandTextures = false;
+    std::string textureCache;  // the reference's cache directory (<name>_lod_<n>.bin); empty: none
 };
 
 void usage(const char *argv0) {
@@ -79,6 +82,10 @@ void usage(const char *argv0) {
               << "  --perf-report <file>   Performance report the run summary is appended to\n"
               << "                         (default: <data>/perf/performance_report.txt)\n"
               << "  --no-textures          Untextured materials (textures load from <data>/textures when present)\n"
+              << "  --bc-textures          Keep the textures as BC7 / BC5 / BC4 blocks, decoded in the sampler\n"
+              << "  --texture-cache <dir>  Read <name>_lod_<n>.bin block files from <dir> (the reference's texture\n"
+              << "                         cache) and write the levels encoded here; implies --bc-textures\n"
+              << "  --expand-textures      With --bc-textures: decode the blocks to RGBA8 texels on the host\n"
               << "  --help, -h             Show this help message\n";
 }
 
@@ -123,6 +130,9 @@ int parse(int argc, char **argv, Options &o) {
         else if (a == "--models") { if ((v = next("--models"))) { o.assetsDir = v; } }
         else if (a == "--perf-report") { if ((v = next("--perf-report"))) { o.perfReport = v; } }
         else if (a == "--no-textures") o.textures = false;
+        else if (a == "--bc-textures") o.bcTextures = true;
+        else if (a == "--expand-textures") o.bcTextures = o.expandTextures = true;
+        else if (a == "--texture-cache") { if ((v = next("--texture-cache"))) { o.textureCache = v; o.bcTextures = true; } }
         else if (a == "--test-sequence") o.testSequence = true;
         else if (a == "--test-remove20") o.removal20 = true;
         else if (a == "--test-remove-circle") o.removalCircle = true;
@@ -266,7 +276,15 @@ int main(int argc, char **argv) {
     if (vxpt_load_settings(ctx) != VXPT_OK) return fail("loading settings");
     if (o.textures) {  // TextureManager::initWithMaterialPaths: every material texture found is used
         int nTex = 0;
-        if (vxpt_load_textures(ctx, nullptr, &nTex) != VXPT_OK) return fail("loading textures");
+        if (o.bcTextures) {
+            int nCached = 0;
+            const int flags = (o.textureCache.empty() ? 0 : VXPT_TEX_WRITE_CACHE) | (o.expandTextures ? VXPT_TEX_EXPAND : 0);
+            if (vxpt_load_textures_bc(ctx, nullptr, o.textureCache.empty() ? nullptr : o.textureCache.c_str(), flags, &nTex,
+                                      &nCached) != VXPT_OK)
+                return fail("loading textures");
+            std::cout << "Block-compressed textures" << (o.expandTextures ? " (expanded to RGBA8)" : "") << ": " << nCached
+                      << " levels from the cache" << std::endl;
+        } else if (vxpt_load_textures(ctx, nullptr, &nTex) != VXPT_OK) return fail("loading textures");
         std::cout << "Textures loaded: " << nTex << (nTex ? "" : " (untextured materials)") << std::endl;
     }
     if (vxpt_generate_terrain(ctx, o.chunks[0], o.chunks[1], o.chunks[2], 32.0f, 32.0f * o.chunks[0], 0) != VXPT_OK)

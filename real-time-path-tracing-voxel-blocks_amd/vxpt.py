@@ -24,7 +24,10 @@ BUF = dict(ILLUM=0, DEPTH=1, NORMAL_ROUGH=2, GEO_NORMAL_THIN=3, ALBEDO=4, MATERI
            PREV_MATERIAL=13, RESERVOIRS=14, PING=15, PONG=16, PREV_ILLUM=17, PREV_FAST=18, HIST_LEN=19,
            PREV_HIST_LEN=20, OUTPUT=21, SKY=32, SUN=33, VOXELS=34, RES_EVEN=35, RES_ODD=36, WPOS=37, FRAME=38,
            OCTANT_TABLES=39, CELL_MASKS=40, BRICK_IDS=41, MACRO_MASKS=42, TEXELS=43, LIGHTS=44,
-           LIGHT_ALIAS=45, BLOOM=46, TAP_RECORD=47, BOX_TABLES=48, CLAMP_DECISION=49)
+           LIGHT_ALIAS=45, BLOOM=46, TAP_RECORD=47, BOX_TABLES=48, CLAMP_DECISION=49, TEX_BLOCKS=50)
+# vxpt_bc_format / vxpt_texture_flags
+BC4, BC5, BC7 = 4, 5, 7
+TEX_WRITE_CACHE, TEX_EXPAND = 1, 2
 FLOAT1_BUFS = {1, 5, 12, 13, 19, 20, 49}
 RESERVOIR_DTYPE = np.dtype([("lightData", "<u4"), ("uvData", "<u4"), ("weightSum", "<f4"), ("targetPdf", "<f4"),
                             ("M", "<f4")])
@@ -146,6 +149,13 @@ def load_library(path=LIB_PATH):
         "vxpt_load_textures": (I, [P, ctypes.c_char_p, P]),
         "vxpt_enable_textures": (I, [P, I]),
         "vxpt_texture_table": (I, [P, P, I, P, P]),
+        "vxpt_load_textures_bc": (I, [P, ctypes.c_char_p, ctypes.c_char_p, I, P, P]),
+        "vxpt_texture_table_bc": (I, [P, P, I, P, P]),
+        "vxpt_bc_decode": (I, [I, P, I, I, P]),
+        "vxpt_bc_encode": (I, [I, P, I, I, P]),
+        "vxpt_bc_cache_path": (I, [ctypes.c_char_p, ctypes.c_char_p, I, P, I]),
+        "vxpt_bc_level": (I, [I, P, I, ctypes.c_char_p, ctypes.c_char_p, I, I, P, P]),
+        "vxpt_probe_texture": (I, [P, I, I, P, P]),
         "vxpt_load_models": (I, [P, ctypes.c_char_p, P]),
         "vxpt_read_obj": (I, [ctypes.c_char_p, P, P, I, P]),
         "vxpt_get_model": (I, [P, I, P, P, I, P]),
@@ -319,6 +329,40 @@ class Renderer:
         self._chk(self.lib.vxpt_load_textures(self.ctx, str(root).encode() if root else None, ctypes.byref(n)),
                   "vxpt_load_textures")
         return n.value
+
+    def load_textures_bc(self, root=None, cache_dir=None, write_cache=False, expand=False):
+        """The texture set as BC7 / BC5 / BC4 blocks (TextureManager.cu:189-330), levels taken from
+        <cache_dir>/<name>_lod_<l>.bin where present; expand: decoded on the host into the RGBA8
+        buffer.  -> (textures loaded, levels taken from cache files)."""
+        n, nc = ctypes.c_int(0), ctypes.c_int(0)
+        flags = (TEX_WRITE_CACHE if write_cache else 0) | (TEX_EXPAND if expand else 0)
+        self._chk(self.lib.vxpt_load_textures_bc(self.ctx, os.fsencode(str(root)) if root else None,
+                                                 os.fsencode(str(cache_dir)) if cache_dir else None, flags,
+                                                 ctypes.byref(n), ctypes.byref(nc)), "vxpt_load_textures_bc")
+        return n.value, nc.value
+
+    def texture_table_bc(self):
+        """[(format, size, maxLod, [level offsets in bytes into TEX_BLOCKS])], total bytes."""
+        n, nb = ctypes.c_int(0), ctypes.c_int64(0)
+        self._chk(self.lib.vxpt_texture_table_bc(self.ctx, None, 0, ctypes.byref(n), ctypes.byref(nb)),
+                  "vxpt_texture_table_bc")
+        out = np.zeros(17 * max(n.value, 1), np.int64)
+        self._chk(self.lib.vxpt_texture_table_bc(self.ctx, _ptr(out), len(out), ctypes.byref(n), ctypes.byref(nb)),
+                  "vxpt_texture_table_bc")
+        tabs, k = [], 0
+        for _ in range(n.value):
+            fmt, size, ml = int(out[k]), int(out[k + 1]), int(out[k + 2])
+            tabs.append((fmt, size, ml, [int(v) for v in out[k + 3:k + 4 + ml]]))
+            k += 4 + ml
+        return tabs, nb.value
+
+    def probe_texture(self, tex_id, uvlod):
+        """uvlod: (n, 3) float32 of (u, v, lod) -> (n, 4) float32, tex2DLod of texture tex_id as the
+        trace kernel samples the loaded set (RGBA8 or blocks)."""
+        q = np.ascontiguousarray(uvlod, np.float32).reshape(-1, 3)
+        out = np.zeros((len(q), 4), np.float32)
+        self._chk(self.lib.vxpt_probe_texture(self.ctx, int(tex_id), len(q), _ptr(q), _ptr(out)), "vxpt_probe_texture")
+        return out
 
     def enable_textures(self, on=True):
         self._chk(self.lib.vxpt_enable_textures(self.ctx, int(bool(on))), "vxpt_enable_textures")
@@ -590,6 +634,8 @@ class Renderer:
             return np.zeros(cx * cy * cz * 32768, np.uint8)
         if which == BUF["TEXELS"]:
             return np.zeros((self.texture_table()[1], 4), np.uint8)
+        if which == BUF["TEX_BLOCKS"]:
+            return np.zeros(self.texture_table_bc()[1], np.uint8)
         if which in (BUF["OCTANT_TABLES"], BUF["CELL_MASKS"], BUF["BRICK_IDS"], BUF["MACRO_MASKS"], BUF["BOX_TABLES"]):
             nb = int(np.prod(self.chunks)) * 512
             return {BUF["OCTANT_TABLES"]: np.zeros(8 * nb, np.uint8), BUF["CELL_MASKS"]: np.zeros(nb, np.uint64),
@@ -811,6 +857,59 @@ def read_png(path):
     if lib.vxpt_read_png(os.fsencode(path), None, None, None, px.ctypes.data, px.size) != 0:
         raise VxptError("cannot read %s" % path)
     return px
+
+
+def bc_bytes_per_block(fmt):
+    return 8 if fmt == BC4 else 16
+
+
+def bc_decode(fmt, blocks, n_blocks_x, n_blocks_y):
+    """Blocks (rows of blocks top-down) -> uint8 [4 n_blocks_y, 4 n_blocks_x, 4]; BC4 -> (v, 0, 0, 255),
+    BC5 -> (v, a, 0, 255).  The body the sampler runs (no GPU needed)."""
+    lib = load_library()
+    b = np.ascontiguousarray(blocks, np.uint8).reshape(-1)
+    if b.size != n_blocks_x * n_blocks_y * bc_bytes_per_block(fmt):
+        raise VxptError("bc_decode: %d bytes for %d x %d blocks" % (b.size, n_blocks_x, n_blocks_y))
+    out = np.zeros((4 * n_blocks_y, 4 * n_blocks_x, 4), np.uint8)
+    if lib.vxpt_bc_decode(int(fmt), _ptr(b), n_blocks_x, n_blocks_y, _ptr(out)) != 0:
+        raise VxptError("vxpt_bc_decode failed")
+    return out
+
+
+def bc_encode(fmt, rgba):
+    """uint8 [h, w, 4] (multiples of 4) -> uint8 block bytes, deterministic (no GPU needed)."""
+    lib = load_library()
+    img = np.ascontiguousarray(rgba, np.uint8)
+    h, w = img.shape[:2]
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise VxptError("bc_encode: RGBA8 expected")
+    out = np.zeros((h // 4) * (w // 4) * bc_bytes_per_block(fmt), np.uint8)
+    if lib.vxpt_bc_encode(int(fmt), _ptr(img), w, h, _ptr(out)) != 0:
+        raise VxptError("vxpt_bc_encode failed")
+    return out
+
+
+def bc_cache_path(cache_dir, tex_path, lod):
+    """The reference's cache file of one level (TextureManager.cu:168-173, 271)."""
+    lib = load_library()
+    buf = ctypes.create_string_buffer(4096)
+    if lib.vxpt_bc_cache_path(os.fsencode(str(cache_dir)), os.fsencode(tex_path), int(lod), buf, len(buf)) != 0:
+        raise VxptError("vxpt_bc_cache_path failed")
+    return os.fsdecode(buf.value)
+
+
+def bc_level(fmt, rgba, tex_path, lod, cache_dir=None, write_cache=False):
+    """One square level as the loader resolves it (no GPU needed) -> (block bytes, taken from the cache)."""
+    lib = load_library()
+    img = np.ascontiguousarray(rgba, np.uint8)
+    size = img.shape[0]
+    out = np.zeros(size * size // 16 * bc_bytes_per_block(fmt), np.uint8)
+    hit = ctypes.c_int(0)
+    if lib.vxpt_bc_level(int(fmt), _ptr(img), size, os.fsencode(str(cache_dir)) if cache_dir else None,
+                         os.fsencode(tex_path), int(lod), TEX_WRITE_CACHE if write_cache else 0, _ptr(out),
+                         ctypes.byref(hit)) != 0:
+        raise VxptError("vxpt_bc_level failed")
+    return out, bool(hit.value)
 
 
 def image_diff(a, b, diff_png=None):
