@@ -66,6 +66,8 @@ enum vxpt_buffer {
                                   * octant (x | y << 8 | z << 16 bricks; 0 = occupied), box_tables.hpp */
     VXPT_BUF_TEX_BLOCKS = 50,    /* read-only: the raw block bytes of a block-compressed texture set
                                   * (vxpt_load_textures_bc without VXPT_TEX_EXPAND; vxpt_texture_table_bc) */
+    VXPT_BUF_FRAME_UPSCALED = 51, /* read-only: the last vxpt_upscale's result, out_w x out_h Float4(rgb, 0):
+                                   * out_w * out_h * 16 B, not W * H */
     VXPT_BUF_CLAMP_DECISION = 49 /* read-only parity hook (vxpt_debug_clamp_decisions): per pixel, a float
                                   * holding the last denoise's history-clamp decision bits -- 1: the x-only
                                   * Float3 compare cmin.x < centre.x (HistoryClamping.h:124), 2: cmax.x >
@@ -387,6 +389,26 @@ int vxpt_postprocess(vxpt_ctx *ctx, const vxpt_post_params *p, float dt_ms);
  * for the RCCL band path, which vxpt_postprocess takes by itself on a context with a communicator):
  * the denoiser output's 1-row halo, the histogram summed over the bands, the bloom's halo */
 int vxpt_postprocess_linked(vxpt_ctx **ctxs, int n, const vxpt_post_params *p, float dt_ms);
+/* Render scale (Backend::dynamicResolution, Backend.cpp:191-232: trace below the output size, then
+ * scale up): VXPT_BUF_FRAME (W x H) -> VXPT_BUF_FRAME_UPSCALED (out_w x out_h float4, alpha 0), on
+ * the context stream.  Call after vxpt_postprocess (or after a vxpt_upload of
+ * VXPT_BUF_FRAME); the frame itself is left as it is.  Modes: Catmull-Rom (BicubicFilter.h), the
+ * 12-tap edge-adaptive upsampler (ScalingFilter.h:124-342), and the upsampler followed by the 3x3
+ * contrast-adaptive sharpener (SharpeningFilter.h) of strength sharpness in [0, 1] (the reference
+ * fixes 1; ignored by the other modes), as a second pass written out of place.
+ * fp32 throughout; texels outside the image are the edge texels.  VXPT_ERR_ARG for out_w < W,
+ * out_h < H, an unknown mode or a sharpness outside [0, 1]; VXPT_ERR_STATE before any frame exists.
+ * The buffer is allocated on first use and regrown when a larger size is asked for.  On a banded
+ * context the call is valid on the rank that holds the gathered frame (vxpt_band_gather of
+ * VXPT_BUF_FRAME); it scales that rank's whole W x H buffer and knows nothing of bands. */
+enum vxpt_upscale_mode { VXPT_UPSCALE_BICUBIC = 0, VXPT_UPSCALE_EASU = 1, VXPT_UPSCALE_EASU_SHARPEN = 2 };
+int vxpt_upscale(vxpt_ctx *ctx, int out_w, int out_h, int mode, float sharpness);
+/* the same per-pixel bodies on the host, bit for bit (no context, no GPU): rgba_in = w*h float4,
+ * rgba_out = out_w*out_h float4.  VXPT_ERR_ARG as above, and for a non-positive w or h */
+int vxpt_upscale_host(const float *rgba_in, int w, int h, float *rgba_out, int out_w, int out_h, int mode,
+                      float sharpness);
+/* size of the last vxpt_upscale and its HIP-event time (waits for it); any pointer may be NULL */
+int vxpt_upscale_info(vxpt_ctx *ctx, int *out_w, int *out_h, float *ms);
 /* OfflineBackend::writeFrameBufferToPNG (OfflineBackend.cpp:191-221): rgba = W*H float4 (the
  * frame), clamped to [0,1], x255 truncated, rows flipped, written as 8-bit RGB PNG */
 int vxpt_write_png_rgba32f(const char *path, int w, int h, const float *rgba);

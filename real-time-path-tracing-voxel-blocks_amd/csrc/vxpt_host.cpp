@@ -32,6 +32,7 @@
 #include "box_tables.hpp"
 #include "bvh_build.hpp"
 #include "light_map.hpp"
+#include "upscale.hpp"
 #include "vx_internal.hpp"
 
 using namespace vx;
@@ -381,6 +382,12 @@ struct vxpt_ctx {
     // planes, luminance histogram, device exposure state
     vxpt_post_params yamlPost{};
     float4 *bloomA = nullptr, *bloomB = nullptr, *frame = nullptr;
+    // render scale (vxpt_upscale): the upscaled frame (followed by the sharpener's input image when that
+    // mode is used), grown on demand; the last call's size and events
+    float4 *upscaled = nullptr;
+    size_t upscaledCap = 0;
+    int upW = 0, upH = 0;
+    hipEvent_t upEv[2] = {};
     unsigned *postHist = nullptr;
     float *postState = nullptr;
     float sunLuminance = 1.0f;     // SkyModel::getAccumulatedSunLuminance: the sun map's total pdf
@@ -678,6 +685,8 @@ bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, 
         case VXPT_BUF_RES_ODD: p = c->res + n; bytes = n * sizeof(Reservoir); return true;
         case VXPT_BUF_WPOS: p = c->wpos; bytes = n * 16; return true;
         case VXPT_BUF_FRAME: p = c->frame; bytes = n * 16; return c->frame != nullptr;
+        case VXPT_BUF_FRAME_UPSCALED:
+            p = c->upscaled; bytes = (size_t)c->upW * c->upH * 16; return !forWrite && c->upW > 0;
         case VXPT_BUF_PING: p = c->ping; bytes = n * 16; return true;
         case VXPT_BUF_PONG: p = c->pong; bytes = n * 16; return true;
         case VXPT_BUF_PREV_ILLUM: p = c->prevIllum; bytes = n * 16; return true;
@@ -1937,6 +1946,8 @@ void vxpt_destroy(vxpt_ctx *c) {
     if (c->haloReady) hipEventDestroy(c->haloReady);
     if (c->haloDone) hipEventDestroy(c->haloDone);
     if (c->exDone) hipEventDestroy(c->exDone);
+    for (hipEvent_t e : c->upEv)
+        if (e) hipEventDestroy(e);
     delete c;
 }
 
@@ -3297,9 +3308,8 @@ int vxpt_get_post_params(vxpt_ctx *c, vxpt_post_params *out) {
 
 namespace {
 
-// the context's post-process arguments (allocating its buffers on first use)
-int post_args(vxpt_ctx *c, const vxpt_post_params *pp, float dtMs, PostArgs &a) {
-    if (!pp) pp = &c->yamlPost;
+// the post-process buffers, allocated on first use
+int post_alloc(vxpt_ctx *c) {
     const size_t n = (size_t)c->W * c->H;
     if (!c->frame) {
         if (dalloc(c, c->bloomA, n) || dalloc(c, c->bloomB, n) ||
@@ -3310,6 +3320,13 @@ int post_args(vxpt_ctx *c, const vxpt_post_params *pp, float dtMs, PostArgs &a) 
         HIPCHK(c, hipMemsetAsync(c->postHist, 0, kPostHist * sizeof(unsigned), c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return VXPT_OK;
+}
+
+// the context's post-process arguments
+int post_args(vxpt_ctx *c, const vxpt_post_params *pp, float dtMs, PostArgs &a) {
+    if (!pp) pp = &c->yamlPost;
+    if (int r = post_alloc(c)) return r;
     a = PostArgs{};
     a.W = c->W; a.H = c->H;
     a.y0 = c->rowBegin; a.y1 = c->rowEnd;
@@ -3380,6 +3397,61 @@ int vxpt_postprocess(vxpt_ctx *c, const vxpt_post_params *pp, float dtMs) {
     PostArgs a;
     if (int r = post_args(c, pp, dtMs, a)) return r;
     HIPCHK(c, launch_postprocess(a, c->stream));
+    return VXPT_OK;
+}
+
+namespace {
+bool upscale_args_ok(int w, int h, int ow, int oh, int mode, float sharpness) {
+    return w > 0 && h > 0 && ow >= w && oh >= h && mode >= VXPT_UPSCALE_BICUBIC && mode <= VXPT_UPSCALE_EASU_SHARPEN &&
+           sharpness >= 0.0f && sharpness <= 1.0f;  // a NaN fails both compares
+}
+}  // namespace
+
+int vxpt_upscale(vxpt_ctx *c, int outW, int outH, int mode, float sharpness) {
+    if (!c) return VXPT_ERR_ARG;
+    if (!upscale_args_ok(c->W, c->H, outW, outH, mode, sharpness))
+        return fail(c, VXPT_ERR_ARG, "vxpt_upscale: output smaller than the frame, unknown mode or sharpness outside [0, 1]");
+    if (!c->frame) return fail(c, VXPT_ERR_STATE, "vxpt_upscale: no frame (vxpt_postprocess or vxpt_upload first)");
+    HIPCHK(c, hipSetDevice(c->dev));
+    const size_t px = (size_t)outW * outH, n = mode == VXPT_UPSCALE_EASU_SHARPEN ? 2 * px : px;
+    if (n > c->upscaledCap) {
+        if (c->upscaled) {  // earlier calls may still read it
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            c->allocs.erase(std::find(c->allocs.begin(), c->allocs.end(), (void *)c->upscaled));
+            HIPCHK(c, hipFree(c->upscaled));
+            c->upscaled = nullptr;
+            c->upscaledCap = 0;
+            c->upW = c->upH = 0;
+        }
+        if (dalloc(c, c->upscaled, n)) return VXPT_ERR_HIP;
+        c->upscaledCap = n;
+    }
+    for (hipEvent_t &e : c->upEv)
+        if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+    HIPCHK(c, hipEventRecord(c->upEv[0], c->stream));
+    HIPCHK(c, launch_upscale(c->frame, c->W, c->H, c->upscaled, c->upscaled + px, outW, outH, mode, sharpness, c->stream));
+    HIPCHK(c, hipEventRecord(c->upEv[1], c->stream));
+    c->upW = outW;
+    c->upH = outH;
+    return VXPT_OK;
+}
+
+int vxpt_upscale_info(vxpt_ctx *c, int *outW, int *outH, float *ms) {
+    if (!c) return VXPT_ERR_ARG;
+    if (c->upW <= 0) return fail(c, VXPT_ERR_STATE, "vxpt_upscale_info: no vxpt_upscale yet");
+    if (outW) *outW = c->upW;
+    if (outH) *outH = c->upH;
+    if (ms) {
+        HIPCHK(c, hipSetDevice(c->dev));
+        HIPCHK(c, hipEventSynchronize(c->upEv[1]));
+        HIPCHK(c, hipEventElapsedTime(ms, c->upEv[0], c->upEv[1]));
+    }
+    return VXPT_OK;
+}
+
+int vxpt_upscale_host(const float *in, int w, int h, float *out, int outW, int outH, int mode, float sharpness) {
+    if (!in || !out || !upscale_args_ok(w, h, outW, outH, mode, sharpness)) return VXPT_ERR_ARG;
+    upscale_host(in, w, h, out, outW, outH, mode, sharpness);
     return VXPT_OK;
 }
 
@@ -3721,6 +3793,8 @@ int vxpt_upload(vxpt_ctx *c, int which, const void *host, size_t bytes) {
     HIPCHK(c, hipSetDevice(c->dev));
     void *p, *mirror;
     size_t n;
+    if (which == VXPT_BUF_FRAME)  // an image to upscale need not come from vxpt_postprocess
+        if (int r = post_alloc(c)) return r;
     // sky, sun and voxels are derived state: set them through their own entry points
     if (!buffer_ptr(c, which, p, n, true, &mirror) || (which >= 32 && which <= 34))
         return fail(c, VXPT_ERR_ARG, "unknown or read-only buffer");

@@ -10,7 +10,10 @@
 // the reference traces 1), --chunks X Y Z (world size, default the reference's 2 1 2), --device,
 // --data (the data directory), --perf-report (the run summary file; default <data>/perf/
 // performance_report.txt, the reference's data/perf/performance_report.txt), and a per-frame CSV
-// <prefix>_frames.csv of the library's timings.
+// <prefix>_frames.csv of the library's timings; --render-scale S traces and post-processes at S times
+// the output size and brings the frame up to it with vxpt_upscale (--upscale, --sharpness) before it
+// is saved: the reference's interactive back end does the same (Backend::dynamicResolution), its
+// offline one does not.
 // The scripted voxel-edit sequences (--test-sequence, --test-remove20, --test-remove-circle) follow
 // the reference's timing: a click set after frame N is picked at frame N+1 against the world as
 // edited so far (VoxelEngine::update, VoxelEngine.cu:906-975) and the geometry changes at frame
@@ -56,7 +59,15 @@ struct Options {
     // block-compressed textures (vxpt_load_textures_bc): blocks decoded in the sampler, or expanded to RGBA8
     bool bcTextures = false, expandTextures = false;
     std::string textureCache;  // the reference's cache directory (<name>_lod_<n>.bin); empty: none
+    // render scale: trace at renderWidth x renderHeight, save width x height (1: no upscale at all)
+    float renderScale = 1.0f, sharpness = 1.0f;
+    int upscaleMode = VXPT_UPSCALE_EASU_SHARPEN;
+    int renderWidth = 0, renderHeight = 0;
 };
+
+const char *upscale_name(int mode) {
+    return mode == VXPT_UPSCALE_BICUBIC ? "bicubic" : mode == VXPT_UPSCALE_EASU ? "easu" : "easu-sharp";
+}
 
 void usage(const char *argv0) {
     std::cout << "Offline Voxel Path Tracer (MI355X)\n"
@@ -86,6 +97,14 @@ void usage(const char *argv0) {
               << "  --texture-cache <dir>  Read <name>_lod_<n>.bin block files from <dir> (the reference's texture\n"
               << "                         cache) and write the levels encoded here; implies --bc-textures\n"
               << "  --expand-textures      With --bc-textures: decode the blocks to RGBA8 texels on the host\n"
+              << "  --render-scale <s>     Trace at s times the output size, 0.25 <= s <= 1 (default: 1); each side is\n"
+              << "                         rounded to a multiple of 8 (at least 8) and the frame is scaled up to\n"
+              << "                         --width x --height before it is saved.  The post-process runs at the\n"
+              << "                         render size, so its crosshair is scaled up with the frame.  1 renders\n"
+              << "                         at the output size as before\n"
+              << "  --upscale <filter>     bicubic | easu | easu-sharp (default: easu-sharp): Catmull-Rom, the\n"
+              << "                         edge-adaptive upsampler, or the upsampler and the sharpener\n"
+              << "  --sharpness <f>        Strength of easu-sharp's sharpener, 0 <= f <= 1 (default: 1)\n"
               << "  --help, -h             Show this help message\n";
 }
 
@@ -133,6 +152,20 @@ int parse(int argc, char **argv, Options &o) {
         else if (a == "--bc-textures") o.bcTextures = true;
         else if (a == "--expand-textures") o.bcTextures = o.expandTextures = true;
         else if (a == "--texture-cache") { if ((v = next("--texture-cache"))) { o.textureCache = v; o.bcTextures = true; } }
+        else if (a == "--render-scale") { if ((v = next("--render-scale"))) { o.renderScale = (float)std::atof(v); } }
+        else if (a == "--sharpness") { if ((v = next("--sharpness"))) { o.sharpness = (float)std::atof(v); } }
+        else if (a == "--upscale") {
+            if ((v = next("--upscale"))) {
+                const std::string m = v;
+                if (m == "bicubic") o.upscaleMode = VXPT_UPSCALE_BICUBIC;
+                else if (m == "easu") o.upscaleMode = VXPT_UPSCALE_EASU;
+                else if (m == "easu-sharp") o.upscaleMode = VXPT_UPSCALE_EASU_SHARPEN;
+                else {
+                    std::cerr << "--upscale takes bicubic, easu or easu-sharp\n";
+                    return -1;
+                }
+            }
+        }
         else if (a == "--test-sequence") o.testSequence = true;
         else if (a == "--test-remove20") o.removal20 = true;
         else if (a == "--test-remove-circle") o.removalCircle = true;
@@ -146,6 +179,25 @@ int parse(int argc, char **argv, Options &o) {
     if (o.totalFrames <= 0 || o.spp <= 0 || o.chunks[0] <= 0 || o.chunks[1] <= 0 || o.chunks[2] <= 0) {
         std::cerr << "frames, spp and chunks must be positive\n";
         return -1;
+    }
+    if (!(o.renderScale >= 0.25f && o.renderScale <= 1.0f) || !(o.sharpness >= 0.0f && o.sharpness <= 1.0f)) {
+        std::cerr << "render-scale must lie in [0.25, 1] and sharpness in [0, 1]\n";
+        return -1;
+    }
+    o.renderWidth = o.width;
+    o.renderHeight = o.height;
+    if (o.renderScale < 1.0f) {
+        if (o.width < 8 || o.height < 8) {
+            std::cerr << "render-scale below 1 needs an output of at least 8x8\n";
+            return -1;
+        }
+        // a multiple of 8, at least 8 and no larger than the output
+        auto side = [&](int out) {
+            const int r = (int)std::lround((double)out * o.renderScale / 8.0) * 8;
+            return std::min(std::max(r, 8), out / 8 * 8);
+        };
+        o.renderWidth = side(o.width);
+        o.renderHeight = side(o.height);
     }
     if (o.perfReport.empty()) o.perfReport = o.dataDir + "/perf/performance_report.txt";
     return 1;
@@ -249,12 +301,16 @@ int main(int argc, char **argv) {
 
     std::cout << "=== Offline Voxel Path Tracer ===\n"
               << "Resolution: " << o.width << "x" << o.height << "\n"
+              << (o.renderScale < 1.0f ? "Render scale: " + std::to_string(o.renderScale) + " (" +
+                                             std::to_string(o.renderWidth) + "x" + std::to_string(o.renderHeight) +
+                                             " traced, " + upscale_name(o.upscaleMode) + " to the resolution)\n"
+                                       : std::string())
               << "Frames to render: " << o.totalFrames << " at " << o.spp << " spp\n"
               << "Output prefix: " << o.outputPrefix << std::endl;
 
     vxpt_config cfg{};
-    cfg.width = o.width;
-    cfg.height = o.height;
+    cfg.width = o.renderWidth;
+    cfg.height = o.renderHeight;
     cfg.device = o.device;
     cfg.total_bounce_limit = 3;    // RayGen.cu:146
     cfg.diffuse_bounce_limit = 1;  // RayGen.cu:147
@@ -342,6 +398,7 @@ int main(int argc, char **argv) {
     std::vector<FrameRecord> perf;
     std::string runStamp;
     const size_t frameBytes = (size_t)o.width * o.height * 4 * sizeof(float);
+    const bool upscale = o.renderScale < 1.0f;
 
     for (int frame = 0; frame < o.totalFrames; frame++) {  // mainOffline.cpp:273-408
         const int frameNumber = frame + 1;
@@ -412,7 +469,9 @@ int main(int argc, char **argv) {
         if (shouldSave) {  // storeFrameInBatch (OfflineBackend.cpp:117-131)
             BatchedFrame b;
             b.rgba.resize((size_t)o.width * o.height * 4);
-            if (vxpt_readback(ctx, VXPT_BUF_FRAME, b.rgba.data(), frameBytes) != VXPT_OK)
+            if (upscale && vxpt_upscale(ctx, o.width, o.height, o.upscaleMode, o.sharpness) != VXPT_OK)
+                return fail("upscaling");
+            if (vxpt_readback(ctx, upscale ? VXPT_BUF_FRAME_UPSCALED : VXPT_BUF_FRAME, b.rgba.data(), frameBytes) != VXPT_OK)
                 return fail("reading the frame");
             b.path = frame_path(o.outputPrefix, frame);
             batch.push_back(std::move(b));
@@ -466,7 +525,9 @@ int main(int argc, char **argv) {
     {  // PerformanceTracker::saveReport: the run summary, and the per-frame rows as a CSV
         const std::string csv = o.outputPrefix + "_frames.csv";
         std::ofstream rep(csv);
-        rep << "# " << o.runComment << "\n# " << o.width << "x" << o.height << ", " << o.spp << " spp\n"
+        rep << "# " << o.runComment << "\n# " << o.width << "x" << o.height << ", " << o.spp << " spp"
+            << (upscale ? ", traced at " + std::to_string(o.renderWidth) + "x" + std::to_string(o.renderHeight) : std::string())
+            << "\n"
             << "frame,trace_ms,denoise_ms,sky_ms,frame_ms,post_ms,wall_ms,dt_ms,comment\n";
         double sumTrace = 0, sumDen = 0, sumWall = 0;
         for (const auto &r : perf) {

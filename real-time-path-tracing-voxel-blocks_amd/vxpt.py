@@ -24,7 +24,10 @@ BUF = dict(ILLUM=0, DEPTH=1, NORMAL_ROUGH=2, GEO_NORMAL_THIN=3, ALBEDO=4, MATERI
            PREV_MATERIAL=13, RESERVOIRS=14, PING=15, PONG=16, PREV_ILLUM=17, PREV_FAST=18, HIST_LEN=19,
            PREV_HIST_LEN=20, OUTPUT=21, SKY=32, SUN=33, VOXELS=34, RES_EVEN=35, RES_ODD=36, WPOS=37, FRAME=38,
            OCTANT_TABLES=39, CELL_MASKS=40, BRICK_IDS=41, MACRO_MASKS=42, TEXELS=43, LIGHTS=44,
-           LIGHT_ALIAS=45, BLOOM=46, TAP_RECORD=47, BOX_TABLES=48, CLAMP_DECISION=49, TEX_BLOCKS=50)
+           LIGHT_ALIAS=45, BLOOM=46, TAP_RECORD=47, BOX_TABLES=48, CLAMP_DECISION=49, TEX_BLOCKS=50,
+           FRAME_UPSCALED=51)
+# vxpt_upscale_mode
+UPSCALE_BICUBIC, UPSCALE_EASU, UPSCALE_EASU_SHARPEN = 0, 1, 2
 # vxpt_bc_format / vxpt_texture_flags
 BC4, BC5, BC7 = 4, 5, 7
 TEX_WRITE_CACHE, TEX_EXPAND = 1, 2
@@ -195,6 +198,9 @@ def load_library(path=LIB_PATH):
         "vxpt_get_post_params": (I, [P, ctypes.POINTER(PostParams)]),
         "vxpt_postprocess": (I, [P, ctypes.POINTER(PostParams), F]),
         "vxpt_postprocess_linked": (I, [ctypes.POINTER(P), I, ctypes.POINTER(PostParams), F]),
+        "vxpt_upscale": (I, [P, I, I, I, F]),
+        "vxpt_upscale_host": (I, [P, I, I, P, I, I, I, F]),
+        "vxpt_upscale_info": (I, [P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(F)]),
         "vxpt_get_sun_projection": (I, [P, P]),
         "vxpt_get_denoise_params": (I, [P, ctypes.POINTER(DenoiseParams)]),
         "vxpt_write_png_rgba32f": (I, [ctypes.c_char_p, I, I, P]),
@@ -528,6 +534,18 @@ class Renderer:
         self._chk(self.lib.vxpt_postprocess(self.ctx, ctypes.byref(params) if params is not None else None,
                                             float(dt_ms)), "vxpt_postprocess")
 
+    def upscale(self, out_w, out_h, mode=UPSCALE_EASU_SHARPEN, sharpness=1.0):
+        """vxpt_upscale: FRAME (W x H) -> FRAME_UPSCALED (out_w x out_h), returned as [out_h, out_w, 4]."""
+        self._chk(self.lib.vxpt_upscale(self.ctx, int(out_w), int(out_h), int(mode), float(sharpness)), "vxpt_upscale")
+        return self.read("FRAME_UPSCALED")
+
+    def upscale_info(self):
+        """(out_w, out_h, HIP-event milliseconds) of the last upscale."""
+        w, h, ms = ctypes.c_int(), ctypes.c_int(), ctypes.c_float()
+        self._chk(self.lib.vxpt_upscale_info(self.ctx, ctypes.byref(w), ctypes.byref(h), ctypes.byref(ms)),
+                  "vxpt_upscale_info")
+        return w.value, h.value, ms.value
+
     def sun_projection(self):
         """(on_screen, px, py, u, v, accumulated sun luminance) of the lens flare."""
         o = np.zeros(6, np.float32)
@@ -642,6 +660,9 @@ class Renderer:
                     BUF["BOX_TABLES"]: np.zeros(8 * nb, np.uint32),
                     BUF["BRICK_IDS"]: np.zeros(nb * 64, np.uint8),
                     BUF["MACRO_MASKS"]: np.zeros(nb // 64, np.uint64)}[which]
+        if which == BUF["FRAME_UPSCALED"]:
+            w, h, _ = self.upscale_info()
+            return np.zeros((h, w, 4), np.float32)
         if which in FLOAT1_BUFS:
             return np.zeros((self.H, self.W), np.float32)
         if which == BUF["TAP_RECORD"]:
@@ -846,6 +867,20 @@ def write_png(path, frame):
     f = np.ascontiguousarray(frame, dtype=np.float32)
     if lib.vxpt_write_png_rgba32f(os.fsencode(path), f.shape[1], f.shape[0], f.ctypes.data) != 0:
         raise VxptError("vxpt_write_png_rgba32f(%s) failed" % path)
+
+
+def upscale_host(image, out_w, out_h, mode=UPSCALE_EASU_SHARPEN, sharpness=1.0):
+    """vxpt_upscale_host: [h, w, 4] float32 -> [out_h, out_w, 4], the kernels' bodies on the host (no GPU needed)."""
+    lib = load_library()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise VxptError("upscale_host: [h, w, 4] float image expected")
+    out = np.zeros((max(int(out_h), 0), max(int(out_w), 0), 4), np.float32)
+    rc = lib.vxpt_upscale_host(_ptr(img), img.shape[1], img.shape[0], _ptr(out), int(out_w), int(out_h), int(mode),
+                               float(sharpness))
+    if rc != 0:
+        raise VxptError("vxpt_upscale_host failed (%d)" % rc)
+    return out
 
 
 def read_png(path):
