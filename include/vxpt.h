@@ -192,6 +192,9 @@ typedef struct vxpt_tuning {
                                  0..1024                                                                 (12) */
     int32_t iter_cap4;        /* with iter_cap3: a fourth level, the level-3 walks resumed for that many more
                                  before the last level (0: off), 0..1024                                   (0) */
+    int32_t brick_pass;       /* 1: a visibility walk crosses an occupied brick that holds no cube in the ray's octant from
+                                 its cell like an empty one (no cell-by-cell walk); 0: every occupied brick
+                                 is walked                                                               (1) */
 } vxpt_tuning;
 int vxpt_tuning_defaults(vxpt_tuning *out);
 int vxpt_get_tuning(vxpt_ctx *ctx, vxpt_tuning *out);

@@ -55,6 +55,27 @@
 #ifndef VX_WPE_RESTIR
 #define VX_WPE_RESTIR 1
 #endif
+// Which walks are compiled with the pass-through of occupied bricks (vx_device.hpp brick_passes, dda_iter's
+// PASS; at run time vxpt_tuning.brick_pass): the camera / path walks of k_closest, k_queue's closest-hit
+// (BRDF-candidate) and visibility walks, the straggler kernels.  Each -D-overridable for A/B builds.
+// Measured per group on the C3 frame: the visibility walks (k_queue<true> and
+// their stragglers) hold the gain; the camera walks and the closest-hit (BRDF-candidate) walks measured
+// even with it, their kernels alone slower, so they are compiled without it.
+#ifndef VX_PASS_CLOSEST
+#define VX_PASS_CLOSEST false
+#endif
+#ifndef VX_PASS_QUEUE_CL
+#define VX_PASS_QUEUE_CL false
+#endif
+#ifndef VX_PASS_QUEUE_OCC
+#define VX_PASS_QUEUE_OCC true
+#endif
+#ifndef VX_PASS_RESUME_CL
+#define VX_PASS_RESUME_CL false
+#endif
+#ifndef VX_PASS_RESUME_OCC
+#define VX_PASS_RESUME_OCC true
+#endif
 
 namespace vx {
 namespace {
@@ -284,8 +305,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_WPE_CLOS
         WorldDev wc = a.world;
         wc.brickSteps = wc.brickStepsCam;
         Hit h;
-        if constexpr (LDS) h = dda_closest<BOX>(wc, o, d, tmax, nullptr, LdsBricks{&cache});
-        else h = dda_closest<BOX>(wc, o, d, tmax VX_IT);
+        if constexpr (LDS) h = dda_closest<BOX, LdsBricks, false, VX_PASS_CLOSEST>(wc, o, d, tmax, nullptr, LdsBricks{&cache});
+        else h = dda_closest<BOX, GlobalBricks, false, VX_PASS_CLOSEST>(wc, o, d, tmax VX_IT);
         w.cHit[s] = pack_hit(h);
         w.cT[s] = h.t;
     }
@@ -423,6 +444,9 @@ VX_D unsigned *straggler_count(const WaveBufs &w, int level, int q, int k) {
     return w.qCount + 2 * kQueues + (((level - 1) * kQueues + q) * kShards + k) * 16;
 }
 
+constexpr bool pass_queue(bool occ) { return occ ? VX_PASS_QUEUE_OCC : VX_PASS_QUEUE_CL; }
+constexpr bool pass_resume(bool occ) { return occ ? VX_PASS_RESUME_OCC : VX_PASS_RESUME_CL; }
+
 template <bool OCC, bool BOX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_WPE_QUEUE))) void k_queue(TraceArgs a, int q, int cap, int shardCap) {
     __shared__ unsigned sTot[4], sBase[4];
@@ -447,7 +471,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_WPE_QUEU
         rc = dda_begin<OCC, BOX>(a.world, xyz(ro), xyz(rd), ro.w, rd.w, st, h);
         // visibility walks may end above the cubes they can still reach (the sky exit, vx_device.hpp):
         // the rays toward the sun and sky that leave the terrain (closest-hit walks measured slower with it)
-        for (int k = 0; rc == DdaRun && k < cap; ++k) rc = dda_iter<OCC, BOX, GlobalBricks, OCC>(a.world, st, h, itp);
+        for (int k = 0; rc == DdaRun && k < cap; ++k) rc = dda_iter<OCC, BOX, GlobalBricks, OCC, pass_queue(OCC)>(a.world, st, h, itp);
     }
 #ifdef VX_STATS
     stat_wave((q & 3) == 1 ? 1 : ((q & 3) == 2 ? 4 : 3), live, iters);
@@ -518,7 +542,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC ? VX_WP
             dda_resume<BOX>(a.world, xyz(ro), xyz(rd), ro.w, rd.w, sv, st);
             rc = DdaRun;
             for (int it = 0; rc == DdaRun && (cap <= 0 || it < cap); ++it)
-                rc = dda_iter<OCC, BOX, GlobalBricks, OCC>(a.world, st, h, itp);  // sky exit: k_queue
+                rc = dda_iter<OCC, BOX, GlobalBricks, OCC, pass_resume(OCC)>(a.world, st, h, itp);  // sky exit: k_queue
         }
 #ifdef VX_STATS
         stat_wave(5, live, iters);
@@ -592,7 +616,7 @@ __global__ __launch_bounds__(256) void k_resume_split(TraceArgs a, int q, int le
         for (;;) {
             const bool run = rc == DdaRun;
             if (__ballot(run) == 0ull) break;
-            if (run) rc = dda_iter<OCC, BOX, GlobalBricks, OCC>(a.world, st, h VX_IT);
+            if (run) rc = dda_iter<OCC, BOX, GlobalBricks, OCC, pass_resume(OCC)>(a.world, st, h VX_IT);
             // (the ballot outside the condition: every lane's event must be seen)
             const unsigned long long evNow = __ballot(rc == DdaEvent);
             if (rc == DdaRun && (evNow & below)) rc = DdaNone;  // an earlier piece has it
@@ -1412,8 +1436,9 @@ VX_D void restir_slot(const TraceArgs &a, int seg, int s, QRays &qr, float4 (*st
                 else { qr.o3 = ts.pos; qr.t3 = tmin; qr.d3 = dir; qr.x3 = tmax; }
             }
         }
-        w.oHit[4 * s + 1 + i] = 0;
     }
+    // oHit[4s + 1 .. 3] cleared for the bias-correction rays' results, oHit[4s] kept: one word (k_finish reads it so)
+    reinterpret_cast<uint32_t *>(w.oHit)[s] = (uint32_t)hit0 & 0xFFu;
     // final visibility: with no tap selected the sample is the RIS one and the
     // ray equals the RIS visibility ray, whose result is already in oHit[4s]
     if (ls.type != LtInvalid && selLoop >= 0) {
@@ -1626,7 +1651,7 @@ __global__ __launch_bounds__(256) void k_probe(WorldDev w, int n, const float *r
         while (rc == DdaRun) {
             const DdaSaved sv = dda_save(st, i);
             dda_resume<BOX>(w, o, d, tmin, r[7], sv, st);
-            rc = occ ? dda_iter<true, BOX, GlobalBricks, true>(w, st, h) : dda_iter<false, BOX, GlobalBricks, true>(w, st, h);
+            rc = occ ? dda_iter<true, BOX, GlobalBricks, true, true>(w, st, h) : dda_iter<false, BOX, GlobalBricks, true, true>(w, st, h);
         }
         if (occ) {
             q[0] = rc == DdaEvent ? 1 : 0;
@@ -1640,12 +1665,12 @@ __global__ __launch_bounds__(256) void k_probe(WorldDev w, int n, const float *r
         return;
     }
     if (mode == 2) {
-        q[0] = dda_occluded<BOX, true>(w, o, d, r[6], r[7]) ? 1 : 0;
+        q[0] = dda_occluded<BOX, true, true>(w, o, d, r[6], r[7]) ? 1 : 0;
         q[1] = q[2] = q[3] = q[4] = q[5] = 0;
         t[i] = 0.0f;
         return;
     }
-    const Hit h = dda_closest<BOX, GlobalBricks, true>(w, o, d, r[7]);
+    const Hit h = dda_closest<BOX, GlobalBricks, true, true>(w, o, d, r[7]);
     q[0] = h.hit; q[1] = h.x; q[2] = h.y; q[3] = h.z; q[4] = h.face; q[5] = h.id;
     t[i] = h.t;
 }

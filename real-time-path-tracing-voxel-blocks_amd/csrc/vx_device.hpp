@@ -415,13 +415,40 @@ VX_HD void dda_seg_start(const WorldDev &w, Dda &s, int D, int P, float T) {
     s.prevLoc = s.nb * 64 + cell_of(c.x, c.y, c.z);
 }
 
+// The cells of the current brick that the walk can still visit: those in the ray's octant from the
+// current cell (per axis the local coordinates from the cell's on in the ray's direction, the cell's
+// alone on an axis that does not move), as a mask in cell_of's bit layout.
+VX_HD uint64_t octant_cells(const Ray3 &r, const Cell &c) {
+    const int lx = c.x & 3, ly = c.y & 3, lz = c.z & 3;
+    const uint32_t x1 = 1u << lx, z1 = 0xFu << (4 * lz);
+    const uint32_t xm = !r.mx ? x1 : (r.sx > 0 ? (0xFu << lx) & 0xFu : (x1 << 1) - 1u);
+    const uint32_t zm = !r.mz ? z1 : (r.sz > 0 ? (0xFFFFu << (4 * lz)) & 0xFFFFu : (0x10u << (4 * lz)) - 1u);
+    uint32_t xz = (xm * 0x1111u) & zm;  // the x mask in every z row, the z rows of the octant
+    xz |= xz << 16;
+    const uint64_t y1 = 0xFFFFull << (16 * ly);
+    const uint64_t ym = !r.my ? y1 : (r.sy > 0 ? ~0ull << (16 * ly) : ~0ull >> (16 * (3 - ly)));
+    return ((uint64_t)xz | ((uint64_t)xz << 32)) & ym;
+}
+// Pass-through (PASS walks, WorldDev::brickPass): the walk stands in an occupied brick, in an empty
+// cell with no cube left behind (prevId 0), and no cube cell of the brick lies in the ray's octant
+// from there: every cell the walk visits in this brick is empty, so no crossing inside it joins or
+// leaves a cube, and the brick is crossed as a 1 x 1 x 1 empty box (skip_box lands on the cell the
+// cell-by-cell walk leaves the brick from, whatever the box holds elsewhere).
+VX_HD bool brick_passes(const WorldDev &w, const Dda &s) {
+    return w.brickPass && s.dist == 0 && s.prevId == 0 && (s.cm & octant_cells(s.r, s.c)) == 0ull;
+}
+
 // SKY: the walk may end above the cubes it can still reach (WorldDev::skyTop, below); a compile-time
-// switch so that the walks without it (camera rays, a queue's first iterations) keep their code
-template <bool OCC, bool BOX = false, class F = GlobalBricks, bool SKY = false>
+// switch so that the walks without it (camera rays, a queue's first iterations) keep their code.
+// PASS: occupied bricks with no cube ahead of the ray are skipped like empty ones (brick_passes).
+template <bool OCC, bool BOX = false, class F = GlobalBricks, bool SKY = false, bool PASS = false>
 VX_HD int dda_iter(const WorldDev &w, Dda &s, Hit &h, int *cnt = nullptr, const F &f = F()) {
     if (++s.steps > w.wx + w.wy + w.wz + 3) return DdaNone;
     if (cnt) ++cnt[s.dist == 0 ? 3 : (s.dist == 1 ? 2 : 1)];
-    if (s.dist == 0) {
+    bool walk = s.dist == 0;
+    if constexpr (PASS)
+        if (brick_passes(w, s)) walk = false;
+    if (walk) {
         const int rc = brick_walk<OCC>(w, s, h, cnt ? cnt + 4 : nullptr);
         if (rc == 1) return DdaEvent;
         if (rc == 2) return DdaNone;
@@ -430,8 +457,12 @@ VX_HD int dda_iter(const WorldDev &w, Dda &s, Hit &h, int *cnt = nullptr, const 
             return DdaRun;
         }
     } else {
-        if constexpr (BOX) skip_box(w, s.r, s.c, (int)(s.box & 0xFFu), (int)((s.box >> 8) & 0xFFu), (int)((s.box >> 16) & 0xFFu));
-        else skip_cube(w, s.r, s.c, s.dist);
+        // (a passed-through brick's table entry is 0: one brick)
+        const int one = PASS ? 1 : 0;
+        if constexpr (BOX)
+            skip_box(w, s.r, s.c, max((int)(s.box & 0xFFu), one), max((int)((s.box >> 8) & 0xFFu), one),
+                     max((int)((s.box >> 16) & 0xFFu), one));
+        else skip_cube(w, s.r, s.c, max(s.dist, one));
     }
     // sky exit, after an empty box (not per cell step): see below
     const bool skyCheck = SKY && s.dist != 0 && w.skyTop && !(s.r.dy < 0.0f);
@@ -465,22 +496,22 @@ VX_HD int dda_iter(const WorldDev &w, Dda &s, Hit &h, int *cnt = nullptr, const 
     return DdaRun;
 }
 
-template <bool BOX = false, class F = GlobalBricks, bool SKY = false>
+template <bool BOX = false, class F = GlobalBricks, bool SKY = false, bool PASS = false>
 VX_HD Hit dda_closest(const WorldDev &w, V3 o, V3 d, float tmax, int *iters = nullptr, const F &f = F()) {
     Hit h{0, 0, 0, 0, -1, 0, kRayMax};
     Dda s;
     int rc = dda_begin<false, BOX>(w, o, d, 0.0f, tmax, s, h, f);
-    while (rc == DdaRun) rc = dda_iter<false, BOX, F, SKY>(w, s, h, iters, f);
+    while (rc == DdaRun) rc = dda_iter<false, BOX, F, SKY, PASS>(w, s, h, iters, f);
     if (rc != DdaEvent) h = Hit{0, 0, 0, 0, -1, 0, kRayMax};
     return h;
 }
 
-template <bool BOX = false, bool SKY = false>
+template <bool BOX = false, bool SKY = false, bool PASS = false>
 VX_HD bool dda_occluded(const WorldDev &w, V3 o, V3 d, float tmin, float tmax, int *iters = nullptr) {
     Hit h;
     Dda s;
     int rc = dda_begin<true, BOX>(w, o, d, tmin, tmax, s, h);
-    while (rc == DdaRun) rc = dda_iter<true, BOX, GlobalBricks, SKY>(w, s, h, iters);
+    while (rc == DdaRun) rc = dda_iter<true, BOX, GlobalBricks, SKY, PASS>(w, s, h, iters);
     return rc == DdaEvent;
 }
 

@@ -82,6 +82,8 @@ struct WorldDev {
                               // (dx > 0) | (dz > 0) << 1 and brick column (bx, bz), 1 + the highest cube cell
                               // row of the columns the quadrant can still reach from it ([q][bz][bx], 0 =
                               // none): a walk not heading down whose cell row is at least that meets no cube
+    int brickPass;            // pass-through (vxpt_tuning.brick_pass): the walks compiled with it skip an occupied
+                              // brick that holds no cube in the ray's octant from the current cell
     int cx, cy, cz;       // chunks
     int wx, wy, wz;       // cells
     int mx, my, mz;       // 16^3 macro cells
