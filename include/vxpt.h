@@ -109,6 +109,15 @@ typedef struct vxpt_denoise_params { /* DenoisingParams, GlobalSettings.h:82-141
     float disocclusion_threshold, disocclusion_threshold_alternate, denoising_range;
     int32_t enable_temporal_accumulation, enable_history_fix, enable_history_clamping;
     int32_t enable_spatial_filtering, enable_firefly_filter, atrous_iteration_num;
+    /* the two stages in front of temporal accumulation (Denoiser.cu:82-92, 101-119), 0 = off (the
+     * reference yaml's values): HitDistReconstruction<8,2> rebuilds the radiance's hit distance (w)
+     * into the ping plane, PrePass blurs the radiance with 8 Poisson taps within 30 pixels.  They use
+     * the reference's hard-coded constants, not the fields above.  The reconstruction alone changes
+     * nothing in the output while temporal accumulation (frame_num > 0) or the spatial filter runs: both
+     * overwrite the ping plane from the un-reconstructed radiance, and the output-source rule
+     * (Denoiser.cu:79-92, 364-373) is applied as written.  It feeds the pre-pass, and the output only
+     * when neither runs.  Banded calls refuse both (VXPT_ERR_STATE, before anything is enqueued). */
+    int32_t enable_hit_distance_reconstruction, enable_pre_pass;
 } vxpt_denoise_params;
 
 typedef struct vxpt_post_params { /* ToneMappingParams + PostProcessingPipelineParams (GlobalSettings.h:10-186),
@@ -360,7 +369,15 @@ int vxpt_denoise(vxpt_ctx *ctx, const vxpt_denoise_params *p, int32_t frame_num,
  * 4 history clamping, 5 a-trous smem, 6 a-trous ping->pong (arg step, arg2 frame index),
  * 7 a-trous pong->ping, 10 final a-trous ping->pong + output, 11 world positions (band +/- 40
  * rows; needed before 0, 3, 5, 6, 7, 10), 12 frame-0 history init, 13 output copy (arg: source
- * 0 illum, 1 ping, 2 pong, 3 prev illum), 14 history copies */
+ * 0 illum, 1 ping, 2 pong, 3 prev illum), 14 history copies, 15 hit-distance reconstruction
+ * (illum -> ping), 16 pre-pass blur (arg = iterationIndex, the rotation of its taps; arg2 = input,
+ * 0 illum or 1 ping; result in illum; with input 0 the radiance is first copied to the ping plane,
+ * which is scratch then: the pass does not run in place).  15 and 16 work on whole frames only:
+ * VXPT_ERR_STATE on a banded context.  The frame calls run them after the firefly filter (which then
+ * writes its filtered pixels back itself) and before the frame-0 init.  A call of pass 15 or 16 leaves
+ * the pass's HIP-event time in vxpt_timings' denoise_ms (the other passes leave it alone).  On a banded
+ * context every pass is refused (VXPT_ERR_STATE) while p has one of the two switches on: a chain composed
+ * from single passes would otherwise drop the stages silently */
 int vxpt_denoise_pass(vxpt_ctx *ctx, const vxpt_denoise_params *p, int pass, int arg, int arg2);
 /* OfflineBackend::renderFrame: spp trace passes (radiance averaged) + denoise.  frame_num as
  * OfflineBackend::m_frameNum; iteration indices frame_num*spp .. +spp-1. */
@@ -378,6 +395,15 @@ int vxpt_render_frames(vxpt_ctx *ctx, const vxpt_denoise_params *p, int32_t fram
 /* the denoiser parameters of global_settings.yaml's `denoising` section (GlobalSettings.h:82-141),
  * the ones every call above uses when p = NULL */
 int vxpt_get_denoise_params(vxpt_ctx *ctx, vxpt_denoise_params *out);
+/* The per-pixel bodies of passes 15 and 16 on the host, bit for bit (no context, no GPU).  stage 0 =
+ * hit-distance reconstruction, 1 = pre-pass blur (iteration_index rotates its taps; ignored by stage
+ * 0).  Planes of w * h pixels: illum and normal_rough float4, depth and material float; cam as for
+ * vxpt_set_camera.  out = w * h float4, not illum itself.  tap_xy (may be NULL; stage 1 only)
+ * receives the texel (x, y) of each pixel's 8 taps, w * h * 8 * 2 int32, before any screen test.
+ * VXPT_ERR_ARG for an unknown stage, a non-positive size or a NULL plane */
+int vxpt_prefilter_host(int stage, int w, int h, const vxpt_camera *cam, int32_t iteration_index,
+                        const float *illum, const float *depth, const float *normal_rough,
+                        const float *material, float *out, int32_t *tap_xy);
 
 /* PostProcessor::run (PostProcessor.cu:74-122): histogram auto-exposure, bloom, lens flare,
  * vignette, filmic tone mapping, crosshair; the denoiser output -> VXPT_BUF_FRAME.  p = NULL

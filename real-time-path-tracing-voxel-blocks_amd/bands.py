@@ -123,7 +123,12 @@ def frame_ops(frame, spp, p, halo=(TRACE_HALO, 2), prev_halo=(TRACE_HALO, 2)):
 
 
 def params_dict(dp):
-    """vxpt.DenoiseParams -> the switches frame_ops needs."""
+    """vxpt.DenoiseParams -> the switches frame_ops needs.  The band schedule has no halo group for the
+    hit-distance reconstruction and the pre-pass: either switch is an error here, as it is
+    in the library's banded calls, not a silently un-blurred chain."""
+    for name in ("enable_hit_distance_reconstruction", "enable_pre_pass"):
+        if getattr(dp, name, 0):
+            raise ValueError("%s is not supported by the band schedule" % name)
     return dict(ta=bool(dp.enable_temporal_accumulation), hf=bool(dp.enable_history_fix),
                 hc=bool(dp.enable_history_clamping), spatial=bool(dp.enable_spatial_filtering),
                 firefly=bool(dp.enable_firefly_filter), iters=int(dp.atrous_iteration_num))

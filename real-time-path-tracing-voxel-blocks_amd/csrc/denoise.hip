@@ -10,10 +10,14 @@
 //   ASmem    AtrousSmem<8,2> (AtrousSmem.h:9-302)
 //   Atrous   Atrous (Atrous.h:6-158), x3; the last one also writes the output
 //            (BufferCopySky + BufferCopyNonSky, BufferCopy.h:6-116 fused in).
+//   hitdist  HitDistReconstruction<8,2> (HitDistReconstruction.h:51-162) and
+//   prepass  PrePass (PrePass.h:6-150), both optional, between the firefly filter and
+//            TA; their per-pixel bodies live in prefilter.hpp, shared with the host.
 // Buffers are SoA float4/float planes, W*H row-major, 16-B lanes (dwordx4).
 // The reference's Float4 operator behaviour (w taken from z) is reproduced
 // because the variance / second-moment channel depends on it.
 #include "vx_internal.hpp"
+#include "prefilter.hpp"
 
 #ifdef VX_EXACT_DENOISE
 // experiment build (libvxpt_exact.so): the reference's compensated dots and IEEE sqrt/exp in
@@ -1397,6 +1401,104 @@ __global__ __launch_bounds__(256) void k_copy_output(DenoiseArgs a, const float4
     }
 }
 
+// ---------------------------------------------------------------- hit-distance reconstruction
+// HitDistReconstruction<8,2> (HitDistReconstruction.h:51-162) on 16x16 tiles: the tile's 5x5
+// neighbourhood (20x20, positions clamped to the screen as Preload does, :30) of the normals, hit
+// distances and |depth| is staged in LDS, one memory round trip (the pixel's own radiance and every
+// staged texel are fetched before the first is used; an apron texel reads only the radiance's w).
+// Supertiles as the other 5x5 LDS stencils (k_history_clamp, k_atrous_smem).  A pixel past the
+// denoising range keeps its radiance (the reference returns without storing).
+struct LdsHit {
+    const float *nx, *ny, *nz, *h, *z;
+    int o;  // the pixel's slot in the 20-wide tile
+    VX_D V3 nrm(int dx, int dy) const {
+        const int k = o + dy * 20 + dx;
+        return V3(nx[k], ny[k], nz[k]);
+    }
+    VX_D float hd(int dx, int dy) const { return h[o + dy * 20 + dx]; }
+    VX_D float vz(int dx, int dy) const { return z[o + dy * 20 + dx]; }
+};
+template <bool ST>
+__global__ __launch_bounds__(256) void k_hitdist(DenoiseArgs a, prefilter::Consts kc, const float4 *in, float4 *out) {
+    constexpr int TS = 16, T = TS + 4, N = T * T, NT = TS * TS, R = (N + NT - 1) / NT, NP = N + 1;
+    static_assert(T == 20, "LdsHit's row stride");
+    const int W = a.W, H = a.H;
+    const int tx = threadIdx.x % TS, ty = threadIdx.x / TS;
+    int btx, bty;
+    if (!map_tile<ST, TS>(a, btx, bty)) return;
+    const int x0 = btx * TS, y0 = a.y0 + bty * TS;
+    const int x = x0 + tx, y = y0 + ty;
+    // one slot more than the tile: every staging store is unconditional (k_history_clamp)
+    __shared__ float sNx[NP], sNy[NP], sNz[NP], sH[NP], sZ[NP];
+    const size_t i = (size_t)min(y, a.y1 - 1) * W + min(x, W - 1);
+    const float4 cI = in[i];
+    V3 vN[R];
+    float vH[R], vZ[R];
+    const float *inw = reinterpret_cast<const float *>(in);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int k = min((int)threadIdx.x + r * NT, N - 1);
+        const size_t j = (size_t)cl(y0 + k / T - 2, H) * W + cl(x0 + k % T - 2, W);
+        vN[r] = xyz4(a.normalRough[j]);
+        vH[r] = inw[4 * j + 3];
+        vZ[r] = a.depth[j];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int k = min((int)threadIdx.x + r * NT, N);
+        sNx[k] = vN[r].x; sNy[k] = vN[r].y; sNz[k] = vN[r].z;
+        sH[k] = vH[r];
+        sZ[k] = fabsf(vZ[r]);
+    }
+    __syncthreads();
+    if (x >= W || y >= a.y1) return;
+    const LdsHit t{sNx, sNy, sNz, sH, sZ, (ty + 2) * T + tx + 2};
+    if (t.vz(0, 0) > prefilter::kRange) {
+        out[i] = cI;
+        return;
+    }
+    out[i] = make_float4(cI.x, cI.y, cI.z, prefilter::hitdist_px(t, kc, W, H, x, y));
+}
+
+// ---------------------------------------------------------------- pre-pass
+// PrePass (PrePass.h:6-150): 8 rotated Poisson taps within 30 pixels, gathered through buffer
+// descriptors (a tap outside the screen has index -1: the hardware range check returns zeros without
+// a memory access, and its weight is 0).  Two round trips: the pixel's own depth, material, normal and
+// radiance (the radius depends on them), then every tap's four values before the first weight.
+// The taps' world positions are recomputed from their depths (4 B per tap; the packed plane
+// DenoiseArgs::wpos would cost 16 B, carries the 16-bit material read instead of the float the
+// reference compares here, and exists only after the firefly pass).  in != a.illum.
+struct PreTapsD {
+    __amdgpu_buffer_rsrc_t rz, rm, rn, rv;
+    VX_D PreTapsD(const DenoiseArgs &a, const float4 *in)
+        : rz(rsrc(a.depth, a.W * a.H * 4)), rm(rsrc(a.material, a.W * a.H * 4)),
+          rn(rsrc(a.normalRough, a.W * a.H * 16)), rv(rsrc(in, a.W * a.H * 16)) {}
+    VX_D float z(int i) const { return ldb1(rz, i); }
+    VX_D float mat(int i) const { return ldb1(rm, i); }
+    VX_D V3 nrm(int i) const { return ldb3(rn, i); }
+    VX_D V4 rad(int i) const { return ldb4(rv, i); }
+};
+template <bool ST>
+__global__ __launch_bounds__(256) void k_prepass(DenoiseArgs a, prefilter::Consts kc, const float4 *in) {
+    int tx, ty;
+    if (!map_tile<ST>(a, tx, ty)) return;
+    const int x = tx * 16 + (threadIdx.x & 15), y = a.y0 + ty * 16 + (threadIdx.x >> 4);
+    if (x >= a.W || y >= a.y1) return;
+    const size_t i = (size_t)y * a.W + x;
+    const float z = a.depth[i], mat = a.material[i];
+    const V3 n = xyz4(a.normalRough[i]);
+    const V4 c = f4(in[i]);
+    if (z > prefilter::kRange) {
+        a.illum[i] = tf(c);
+        return;
+    }
+    a.illum[i] = tf(prefilter::prepass_px(PreTapsD(a, in), a.cam, kc, a.W, a.H, x, y, c, z, mat, n));
+}
+__global__ __launch_bounds__(256) void k_copy4(const float4 *in, float4 *out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = in[i];
+}
+
 // 16x16 tiles over the band rows [y0, y1)
 inline dim3 grid16(const DenoiseArgs &a) { return dim3((a.W + 15) / 16, (a.y1 - a.y0 + 15) / 16); }
 // xcd_tile<TS>'s grid: 8 strips x the widest strip's tiles
@@ -1485,6 +1587,46 @@ hipError_t launch_atrous(const DenoiseArgs &a, const float4 *in, float4 *out, un
     else  // step 8: a 34x34 staged apron for 16x16 pixels was measured slower (71 vs 65 us) than the taps
         hipLaunchKernelGGL(k_atrous, grid_xcd(a), dim3(256), 0, st, a, in, out, step, frameIndex, f);
     return hipGetLastError();
+}
+hipError_t launch_hitdist(const DenoiseArgs &a, hipStream_t st) {
+    const prefilter::Consts kc = prefilter::make_consts(a.cam, a.W, a.H, 0);
+    hipLaunchKernelGGL((k_hitdist<true>), grid_st(a), dim3(256), 0, st, a, kc, (const float4 *)a.illum, a.ping);
+    return hipGetLastError();
+}
+hipError_t launch_prepass(const DenoiseArgs &a, int iterationIndex, bool fromPing, hipStream_t st) {
+    const prefilter::Consts kc = prefilter::make_consts(a.cam, a.W, a.H, iterationIndex);
+    if (!fromPing) {
+        const size_t n = (size_t)a.W * a.H;
+        hipLaunchKernelGGL(k_copy4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)a.illum, a.ping, n);
+    }
+    hipLaunchKernelGGL((k_prepass<true>), grid_st(a), dim3(256), 0, st, a, kc, (const float4 *)a.ping);
+    return hipGetLastError();
+}
+void prefilter_host(int stage, const CamDev &cam, int w, int h, int iterationIndex, const float *illum,
+                    const float *depth, const float *normalRough, const float *material, float *out, int32_t *tapXY) {
+    const prefilter::Consts kc = prefilter::make_consts(cam, w, h, iterationIndex);
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t i = (size_t)y * w + x;
+            const float *ci = illum + 4 * i;
+            float *o = out + 4 * i;
+            if (stage == prefilter::kStageHitDist) {
+                const prefilter::HostHit t{illum, depth, normalRough, w, h, x, y};
+                o[0] = ci[0]; o[1] = ci[1]; o[2] = ci[2];
+                o[3] = t.vz(0, 0) > prefilter::kRange ? ci[3] : prefilter::hitdist_px(t, kc, w, h, x, y);
+                continue;
+            }
+            const float z = depth[i];
+            if (tapXY) {
+                const float radius = prefilter::blur_radius(kc, z, ci[3]);
+                for (int k = 0; k < 8; ++k) prefilter::tap_texel(kc, w, h, x, y, radius, k, tapXY[(i * 8 + k) * 2], tapXY[(i * 8 + k) * 2 + 1]);
+            }
+            V4 r(ci[0], ci[1], ci[2], ci[3]);
+            if (!(z > prefilter::kRange))
+                r = prefilter::prepass_px(prefilter::HostPre{illum, depth, normalRough, material}, cam, kc, w, h, x, y, r, z,
+                                          material[i], V3(normalRough[4 * i], normalRough[4 * i + 1], normalRough[4 * i + 2]));
+            o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
+        }
 }
 hipError_t launch_copy_output(const DenoiseArgs &a, const float4 *in, hipStream_t st) {
     hipLaunchKernelGGL(k_copy_output, grid1d(a), dim3(256), 0, st, a, in);

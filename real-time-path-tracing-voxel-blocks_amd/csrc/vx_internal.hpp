@@ -281,6 +281,7 @@ struct DenoiseParamsDev {
     float maxAcc, maxFast, phiL, lobeAngleFraction, roughnessFraction, depthThreshold;
     float disocclusionThreshold, disocclusionThresholdAlternate, denoisingRange;
     int enableTA, enableHF, enableHC, enableSpatial, enableFirefly, atrousIterations;
+    int enableHitDist, enablePrePass;  // host side only: the chain launches k_hitdist / k_prepass
 };
 
 struct DenoiseArgs {

@@ -32,6 +32,7 @@
 #include "box_tables.hpp"
 #include "bvh_build.hpp"
 #include "light_map.hpp"
+#include "prefilter.hpp"
 #include "upscale.hpp"
 #include "vx_internal.hpp"
 
@@ -606,7 +607,8 @@ void fill_denoise(vxpt_ctx *c, const vxpt_denoise_params *p, DenoiseArgs &a, int
            p->lobe_angle_fraction, p->roughness_fraction, p->depth_threshold, p->disocclusion_threshold,
            p->disocclusion_threshold_alternate, p->denoising_range, p->enable_temporal_accumulation,
            p->enable_history_fix, p->enable_history_clamping, p->enable_spatial_filtering,
-           p->enable_firefly_filter, p->atrous_iteration_num};
+           p->enable_firefly_filter, p->atrous_iteration_num, p->enable_hit_distance_reconstruction,
+           p->enable_pre_pass};
     const GSlot &g = c->gb[c->last];
     a.illum = c->denoiseInputIsAccum ? c->accum : c->illum;
     a.normalRough = g.normalRough;
@@ -655,7 +657,7 @@ vxpt_post_params default_post() {
 }
 
 const vxpt_denoise_params &default_denoise() {
-    static vxpt_denoise_params d{30.f, 6.f, 2.f, 0.5f, 0.15f, 0.003f, 0.01f, 0.05f, 500000.f, 1, 1, 1, 1, 1, 1};
+    static vxpt_denoise_params d{30.f, 6.f, 2.f, 0.5f, 0.15f, 0.003f, 0.01f, 0.05f, 500000.f, 1, 1, 1, 1, 1, 1, 0, 0};
     return d;
 }
 
@@ -1146,18 +1148,38 @@ hipError_t firefly_band(const DenoiseArgs &a, bool detect, bool apply, hipStream
 
 // Denoiser::run (Denoiser.cu:24-408) on the context stream.  (Running all of it but the firefly
 // stage on a third stream beside the next frame's first pass was measured and removed)
+// The two stages in front of temporal accumulation have no band schedule (the pre-pass reaches 30 rows,
+// the reconstruction 2: a halo group of their own): the switch a banded call must refuse
+const char *prefilter_switch(const vxpt_denoise_params *p) {
+    if (p->enable_hit_distance_reconstruction) return "enable_hit_distance_reconstruction";
+    if (p->enable_pre_pass) return "enable_pre_pass";
+    return nullptr;
+}
+int refuse_prefilter(vxpt_ctx *c, const char *sw) {
+    return fail(c, VXPT_ERR_STATE, (std::string(sw) + " is not supported on banded contexts (a row range, a band "
+                                    "communicator or linked contexts)").c_str());
+}
+bool is_banded(const vxpt_ctx *c) { return c->rowBegin != 0 || c->rowEnd != c->H || c->comm || !c->linked.empty(); }
+
 int do_denoise(vxpt_ctx *c, const vxpt_denoise_params *p, int frameNum, int it) {
     if (!p) p = &c->yamlDenoise;
+    const bool recon = p->enable_hit_distance_reconstruction != 0, pre = p->enable_pre_pass != 0;
+    if ((recon || pre) && is_banded(c)) return refuse_prefilter(c, prefilter_switch(p));
     const int used = it > 0 ? it - 1 : 0;
     DenoiseArgs a{};
     fill_denoise(c, p, a, used & 1);
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     // the temporal pass applies the firefly lists when it runs
-    const bool ffFold = p->enable_temporal_accumulation && frameNum > 0;
+    // (the two optional stages read the filtered radiance: the firefly pass then applies its own lists)
+    const bool ffFold = p->enable_temporal_accumulation && frameNum > 0 && !recon && !pre;
     HIPCHK(c, firefly_band(a, p->enable_firefly_filter, !ffFold, c->stream));
     hipStream_t st = c->stream;
-    if (frameNum == 0) HIPCHK(c, launch_frame0_init(a, st));
     int fin = 0;  // 0 illum, 1 ping, 2 pong, 3 prevIllum
+    // Denoiser.cu:79-92: the reconstruction alone moves the result to the ping plane; :101-119: the
+    // pre-pass reads this frame's radiance (the reconstruction's output if it ran) and writes illum
+    if (recon) { HIPCHK(c, launch_hitdist(a, st)); fin = 1; }
+    if (pre) HIPCHK(c, launch_prepass(a, it, recon, st));
+    if (frameNum == 0) HIPCHK(c, launch_frame0_init(a, st));
     if (p->enable_temporal_accumulation && frameNum > 0) {
         HIPCHK(c, launch_temporal(a, st));
         fin = 1;
@@ -1197,6 +1219,9 @@ int do_denoise(vxpt_ctx *c, const vxpt_denoise_params *p, int frameNum, int it) 
 // the context's rows (8-aligned, clipped to the frame) -- the rows a later pass of the chain reads there,
 // computed here from the same inputs as the neighbour computes them instead of received from it
 int run_pass(vxpt_ctx *c, const vxpt_denoise_params *p, int pass, int arg, int arg2, int margin = 0) {
+    // a chain composed from single passes on a banded context (bands.py) would drop the two stages silently
+    if (const char *sw = prefilter_switch(p))
+        if (is_banded(c)) return refuse_prefilter(c, sw);
     DenoiseArgs a{};
     fill_denoise(c, p, a, pass == 0 ? (arg & 1) : 0);
     a.y0 = std::max(0, a.y0 - margin);
@@ -1217,6 +1242,13 @@ int run_pass(vxpt_ctx *c, const vxpt_denoise_params *p, int pass, int arg, int a
             HIPCHK(c, launch_copy_output(a, src, c->stream));
         } break;
         case 14: HIPCHK(c, history_copies(c)); break;
+        case 15:
+        case 16:
+            if (is_banded(c))
+                return refuse_prefilter(c, pass == 15 ? "enable_hit_distance_reconstruction" : "enable_pre_pass");
+            if (pass == 15) HIPCHK(c, launch_hitdist(a, c->stream));
+            else HIPCHK(c, launch_prepass(a, arg, arg2 == 1, c->stream));
+            break;
         default: return fail(c, VXPT_ERR_ARG, "unknown pass");
     }
     return VXPT_OK;
@@ -1605,6 +1637,7 @@ void band_timings(std::vector<vxpt_ctx *> &cs) {
 // this frame's chain (vxpt_render_frames' host gate: no front stream parked behind a wait for it).
 int band_frame(std::vector<vxpt_ctx *> &cs, const vxpt_denoise_params *p, int frame, int spp, bool sync = true,
                std::vector<PassPlan> *pipe = nullptr, bool pipeNext = false) {
+    if (const char *sw = prefilter_switch(p)) return refuse_prefilter(cs[0], sw);
     const int it0 = frame * spp;
     // halo depths for this frame's camera motion; the previous frame exchanged its last pass's
     // rows and the histories for its own camera: top them up before the first pass reads them
@@ -1979,6 +2012,8 @@ int vxpt_load_settings(vxpt_ctx *c) {
             else if (key == "enableHistoryClamping") d.enable_history_clamping = as_bool(val);
             else if (key == "enableSpatialFiltering") d.enable_spatial_filtering = as_bool(val);
             else if (key == "enableFireflyFilter") d.enable_firefly_filter = as_bool(val);
+            else if (key == "enableHitDistanceReconstruction") d.enable_hit_distance_reconstruction = as_bool(val);
+            else if (key == "enablePrePass") d.enable_pre_pass = as_bool(val);
             else if (key == "maxAccumulatedFrameNum") d.max_accumulated_frame_num = v;
             else if (key == "maxFastAccumulatedFrameNum") d.max_fast_accumulated_frame_num = v;
             else if (key == "phiLuminance") d.phi_luminance = v;
@@ -3063,14 +3098,26 @@ int vxpt_denoise_pass(vxpt_ctx *c, const vxpt_denoise_params *p, int pass, int a
     if (!c) return VXPT_ERR_ARG;
     if (!p) p = &c->yamlDenoise;
     HIPCHK(c, hipSetDevice(c->dev));
+    // passes 15 and 16 alone are timed (tools/prefilter_bench.py); every other pass is as it was
+    const bool timed = (pass == 15 || pass == 16) && !is_banded(c);
+    if (timed) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     if (int r = run_pass(c, p, pass, arg, arg2)) return r;
+    if (timed) HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        c->timing.denoise_ms = ms;
+    }
     return VXPT_OK;
 }
 
 int vxpt_render_frame(vxpt_ctx *c, const vxpt_denoise_params *p, int32_t frameNum, int32_t spp) {
     if (!c || spp < 1) return VXPT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->dev));
+    // refused before anything is enqueued: the context is left as it was
+    if (const char *sw = prefilter_switch(p ? p : &c->yamlDenoise))
+        if (is_banded(c)) return refuse_prefilter(c, sw);
     if (c->comm) {
         std::vector<vxpt_ctx *> cs{c};
         return band_frame(cs, p ? p : &cs[0]->yamlDenoise, frameNum, spp);
@@ -3098,6 +3145,9 @@ int vxpt_render_frame(vxpt_ctx *c, const vxpt_denoise_params *p, int32_t frameNu
 int vxpt_render_frames(vxpt_ctx *c, const vxpt_denoise_params *p, int32_t frame0, int32_t nFrames, int32_t spp) {
     if (!c || spp < 1 || nFrames < 1 || frame0 < 0) return VXPT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->dev));
+    // refused before anything is enqueued: the context is left as it was
+    if (const char *sw = prefilter_switch(p ? p : &c->yamlDenoise))
+        if (is_banded(c)) return refuse_prefilter(c, sw);
     const auto hostT0 = std::chrono::steady_clock::now();
     auto hostMs = [&]() {
         return (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - hostT0).count() /
@@ -3456,6 +3506,17 @@ int vxpt_upscale_info(vxpt_ctx *c, int *outW, int *outH, float *ms) {
 int vxpt_upscale_host(const float *in, int w, int h, float *out, int outW, int outH, int mode, float sharpness) {
     if (!in || !out || !upscale_args_ok(w, h, outW, outH, mode, sharpness)) return VXPT_ERR_ARG;
     upscale_host(in, w, h, out, outW, outH, mode, sharpness);
+    return VXPT_OK;
+}
+
+int vxpt_prefilter_host(int stage, int w, int h, const vxpt_camera *cam, int32_t iterationIndex, const float *illum,
+                        const float *depth, const float *normalRough, const float *material, float *out,
+                        int32_t *tapXY) {
+    if ((stage != 0 && stage != 1) || w < 1 || h < 1 || !cam || !illum || !depth || !normalRough || !material || !out ||
+        illum == out)
+        return VXPT_ERR_ARG;
+    prefilter_host(stage, make_camera(w, h, *cam, nullptr, nullptr), w, h, iterationIndex, illum, depth, normalRough,
+                   material, out, stage == 1 ? tapXY : nullptr);
     return VXPT_OK;
 }
 

@@ -64,7 +64,9 @@ class DenoiseParams(ctypes.Structure):
         "roughness_fraction", "depth_threshold", "disocclusion_threshold", "disocclusion_threshold_alternate",
         "denoising_range")] + [(n, ctypes.c_int32) for n in (
             "enable_temporal_accumulation", "enable_history_fix", "enable_history_clamping",
-            "enable_spatial_filtering", "enable_firefly_filter", "atrous_iteration_num")]
+            "enable_spatial_filtering", "enable_firefly_filter", "atrous_iteration_num",
+            # the two stages in front of temporal accumulation; omitted trailing arguments are 0 = off
+            "enable_hit_distance_reconstruction", "enable_pre_pass")]
 
     @classmethod
     def defaults(cls):
@@ -201,6 +203,7 @@ def load_library(path=LIB_PATH):
         "vxpt_postprocess_linked": (I, [ctypes.POINTER(P), I, ctypes.POINTER(PostParams), F]),
         "vxpt_upscale": (I, [P, I, I, I, F]),
         "vxpt_upscale_host": (I, [P, I, I, P, I, I, I, F]),
+        "vxpt_prefilter_host": (I, [I, I, I, ctypes.POINTER(Camera), I, P, P, P, P, P, P]),
         "vxpt_upscale_info": (I, [P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(F)]),
         "vxpt_get_sun_projection": (I, [P, P]),
         "vxpt_get_denoise_params": (I, [P, ctypes.POINTER(DenoiseParams)]),
@@ -882,6 +885,32 @@ def upscale_host(image, out_w, out_h, mode=UPSCALE_EASU_SHARPEN, sharpness=1.0):
     if rc != 0:
         raise VxptError("vxpt_upscale_host failed (%d)" % rc)
     return out
+
+
+PREFILTER_HIT_DIST, PREFILTER_PRE_PASS = 0, 1
+
+
+def prefilter_host(stage, illum, depth, normal_rough, material, camera, iteration_index=0, taps=False):
+    """vxpt_prefilter_host: the bodies of denoiser passes 15 (stage 0, hit-distance reconstruction) and 16
+    (stage 1, pre-pass blur) on the host (no GPU needed).  illum and normal_rough [h, w, 4], depth and
+    material [h, w] float32; camera = (pos, dir, fov_deg).  Returns the [h, w, 4] result, and with taps
+    (stage 1) also the [h, w, 8, 2] int32 texels (x, y) of every pixel's taps."""
+    lib = load_library()
+    il = np.ascontiguousarray(illum, dtype=np.float32)
+    h, w = il.shape[:2]
+    z = np.ascontiguousarray(depth, dtype=np.float32)
+    nr = np.ascontiguousarray(normal_rough, dtype=np.float32)
+    m = np.ascontiguousarray(material, dtype=np.float32)
+    if il.shape != (h, w, 4) or nr.shape != (h, w, 4) or z.shape != (h, w) or m.shape != (h, w):
+        raise VxptError("prefilter_host: [h, w, 4] illum / normal_rough and [h, w] depth / material expected")
+    cam = Camera((ctypes.c_float * 3)(*camera[0]), (ctypes.c_float * 3)(*camera[1]), float(camera[2]))
+    out = np.zeros((h, w, 4), np.float32)
+    xy = np.zeros((h, w, 8, 2), np.int32) if taps else None
+    rc = lib.vxpt_prefilter_host(int(stage), w, h, ctypes.byref(cam), int(iteration_index), _ptr(il), _ptr(z), _ptr(nr),
+                                 _ptr(m), _ptr(out), _ptr(xy) if taps else None)
+    if rc != 0:
+        raise VxptError("vxpt_prefilter_host failed (%d)" % rc)
+    return (out, xy) if taps else out
 
 
 def read_png(path):
