@@ -68,6 +68,9 @@ enum vxpt_buffer {
                                   * (vxpt_load_textures_bc without VXPT_TEX_EXPAND; vxpt_texture_table_bc) */
     VXPT_BUF_FRAME_UPSCALED = 51, /* read-only: the last vxpt_upscale's result, out_w x out_h Float4(rgb, 0):
                                    * out_w * out_h * 16 B, not W * H */
+    VXPT_BUF_SKY_PDF = 52,       /* read-only: 1024*512 floats, the sky map's luminance (the sky table's weights) */
+    VXPT_BUF_SUN_PDF = 53,       /* read-only: 32*32 floats, the sun map's luminance (the sun table's weights)    */
+    VXPT_BUF_SUN_ALIAS = 54,     /* read-only: 32*32 x {f32 q, f32 p, i32 alias}, the sun map's alias table       */
     VXPT_BUF_CLAMP_DECISION = 49 /* read-only parity hook (vxpt_debug_clamp_decisions): per pixel, a float
                                   * holding the last denoise's history-clamp decision bits -- 1: the x-only
                                   * Float3 compare cmin.x < centre.x (HistoryClamping.h:124), 2: cmax.x >
@@ -240,6 +243,29 @@ int vxpt_upload_materials(vxpt_ctx *ctx, const vxpt_material *mats, int n_block_
 /* SkyModel::update (Sky.cu:355-396): sky + sun maps on the GPU, alias tables on the host */
 int vxpt_set_sky(vxpt_ctx *ctx, float time_of_day, float sun_axis_angle_deg, float sun_axis_rotate_deg,
                  float brightness);
+/* The same sky built without leaving the device, for a sky that moves between frames (a time-of-day
+ * run).  The maps are vxpt_set_sky's, except that the upper hemisphere's sum, which sets the lower
+ * hemisphere's mist colour, is reduced on the device in a fixed tree order (csrc/alias_build.hpp)
+ * instead of sequentially: it may differ by one float ulp, and the lower hemisphere with it.  The two
+ * alias tables are NOT Vose's: they come from the parallel construction of csrc/alias_build.hpp
+ * (vxpt_alias_build below), equally valid tables with another pairing, so a sampled frame differs
+ * from vxpt_set_sky's by noise, not by bias.  The call is enqueued on the context stream and returns
+ * without waiting; a frame enqueued right after it sees the new sky (the front streams wait for the
+ * build).  Nothing is allocated after the first call; no map, pdf plane or table crosses to the
+ * host -- only the three sums (48 bytes) are copied back, asynchronously, because the sun table's sum
+ * is an argument of the post-process.  vxpt_get_sky_alias reads the table back on demand, and
+ * vxpt_timings waits for the build to report sky_ms.  Banded and linked contexts: call it on every
+ * member; each builds its own tables, and the integer construction makes them bit-identical. */
+int vxpt_set_sky_device(vxpt_ctx *ctx, float time_of_day, float sun_axis_angle_deg, float sun_axis_rotate_deg,
+                        float brightness);
+/* The parallel alias construction (csrc/alias_build.hpp: Vose's inputs p = w / sum and s = p * n, s in
+ * 40-bit fixed point, then a stable light / heavy partition, two prefix sums and two binary searches
+ * per bin) of n <= 2^22 weights: q, p, alias (-1 = none) per bin and the weights' sum; any output may
+ * be null.  vxpt_alias_build_host is the host twin and needs no context; vxpt_alias_build runs the
+ * kernels vxpt_set_sky_device uses on the same input (a parity hook: it allocates, copies and waits).
+ * The two agree bit for bit. */
+int vxpt_alias_build_host(const float *w, int n, float *q, float *p, int32_t *alias, float *sum);
+int vxpt_alias_build(vxpt_ctx *ctx, const float *w, int n, float *q, float *p, int32_t *alias, float *sum);
 /* RenderCamera camera/historyCamera (mainOffline.cpp:227-251) */
 int vxpt_set_camera(vxpt_ctx *ctx, const vxpt_camera *cur, const vxpt_camera *prev);
 /* Camera matrices as the kernels see them: pos3 dir3 uvToWorld9 worldToUv9 res2 invRes2 tanHalfFov2 yaw pitch */
@@ -570,10 +596,13 @@ int vxpt_debug_clamp_decisions(vxpt_ctx *ctx, int on);
  * the records, not the planes, between passes). */
 int vxpt_readback(vxpt_ctx *ctx, int which, void *host, size_t bytes);
 int vxpt_upload(vxpt_ctx *ctx, int which, const void *host, size_t bytes);
-/* sky alias table (Vose, AliasTable.cu:66-153): q,p floats and alias ints, 1024*512 each */
+/* sky alias table (Vose, AliasTable.cu:66-153; after vxpt_set_sky_device the device-built one, read
+ * back by this call): q,p floats and alias ints, 1024*512 each */
 int vxpt_get_sky_alias(vxpt_ctx *ctx, float *q, float *p, int32_t *alias, float sun_dir[3]);
 int vxpt_timings(vxpt_ctx *ctx, vxpt_timing *out);
 int vxpt_sync(vxpt_ctx *ctx);
+/* free and total memory of the context's device, bytes (hipMemGetInfo; either may be null) */
+int vxpt_device_memory(vxpt_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 /* raw stream handle (hipStream_t) for hosts that enqueue their own work */
 void *vxpt_stream(vxpt_ctx *ctx);
 /* DDA probe: n rays (o3 d3 tmin tmax) -> n x (hit x y z face id) + t; mode 0 closest, 2 occluded;

@@ -126,7 +126,209 @@ __global__ __launch_bounds__(256) void k_sky_lower(float4 *sky, float *pdf, int 
     pdf[i] = luminance(c);
 }
 
+// the same with the upper hemisphere's sum read from device memory (vxpt_set_sky_device)
+__global__ __launch_bounds__(256) void k_sky_lower_dev(float4 *sky, float *pdf, int W, int H, const AliasHead *upper) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int half = H / 2;
+    if (x >= W || y >= half) return;
+    const float sumUpper = upper->fsum;
+    const float v = ((float)y + 0.5f) / (float)half - 1.0f;
+    const V3 mist(sumUpper / (float)(W * H));
+    const float blend = clampf((v + 0.4f) * (1.0f / 0.5f));
+    const float4 e = sky[(size_t)W * half + x];
+    const V3 em(e.x, e.y, e.z);
+    const V3 c = mist + (blend * blend * (3.0f - 2.0f * blend)) * (em - mist);  // smoothstep3f
+    const size_t i = (size_t)W * y + x;
+    sky[i] = make_float4(c.x, c.y, c.z, 0.0f);
+    pdf[i] = luminance(c);
+}
+
+// ---- the parallel alias construction (alias_build.hpp): 256 lanes x 4 consecutive items per workgroup.
+// The scans are reduce (k_ab_classify) / scan of the workgroup sums in one workgroup (k_ab_scan_blocks) /
+// downsweep (k_ab_scatter) in separate launches: no workgroup ever waits for another.
+
+// halving fold of 256 doubles in LDS (tree_sum's order); the result is in v[0]
+VX_D void fold256_lds(double *v, int t) {
+    for (int h = ab::kLanes / 2; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (t < h) v[t] += v[t + h];
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_ab_sum1(const float *w, int n, double *part) {
+    __shared__ double v[ab::kLanes];
+    const int t = threadIdx.x;
+    v[t] = ab::lane_sum(w, n, blockIdx.x, t);
+    fold256_lds(v, t);
+    if (t == 0) part[blockIdx.x] = v[0];
+}
+
+__global__ __launch_bounds__(256) void k_ab_sum2(const double *part, int chunks, AliasHead *head) {
+    __shared__ double v[ab::kLanes];
+    const int t = threadIdx.x;
+    v[t] = ab::top_lane_sum(part, chunks, t);
+    fold256_lds(v, t);
+    if (t == 0) {
+        head->sum = v[0];
+        head->fsum = (float)v[0];
+    }
+}
+
+VX_D AliasTuple tuple_add(AliasTuple a, const AliasTuple &b) {
+    a.d += b.d; a.e += b.e; a.nl += b.nl;
+    return a;
+}
+// one item's contribution
+VX_D AliasTuple tuple_of(int64_t f) {
+    AliasTuple r{0, 0, 0, 0};
+    if (f < ab::kOne) { r.d = ab::kOne - f; r.nl = 1; }
+    else r.e = f - ab::kOne;
+    return r;
+}
+
+// inclusive scan of 256 tuples in LDS (integers: any order gives the same bits); returns lane t's
+VX_D AliasTuple scan256_lds(AliasTuple *v, int t, AliasTuple mine) {
+    v[t] = mine;
+    for (int off = 1; off < ab::kLanes; off <<= 1) {
+        __syncthreads();
+        AliasTuple o{0, 0, 0, 0};
+        if (t >= off) o = v[t - off];
+        __syncthreads();
+        if (t >= off) v[t] = tuple_add(v[t], o);
+    }
+    __syncthreads();
+    return v[t];
+}
+
+// p = w / sum, and each workgroup's (lights, deficit, excess) totals
+__global__ __launch_bounds__(256) void k_ab_classify(const float *w, int n, const AliasHead *head, AliasBin *out,
+                                                      AliasTuple *blk) {
+    __shared__ AliasTuple v[ab::kLanes];
+    const int t = threadIdx.x;
+    const float fsum = head->fsum;
+    AliasTuple mine{0, 0, 0, 0};
+    const int base = blockIdx.x * ab::kChunk + t * ab::kPerLane;
+    for (int k = 0; k < ab::kPerLane; ++k) {
+        const int i = base + k;
+        if (i >= n) break;
+        const float p = ab::prob(w[i], fsum);
+        out[i].p = p;
+        mine = tuple_add(mine, tuple_of(ab::fixed(ab::scaled(p, n))));
+    }
+    const AliasTuple inc = scan256_lds(v, t, mine);
+    if (t == ab::kLanes - 1) blk[blockIdx.x] = inc;
+}
+
+// exclusive scan of the workgroup totals, in place, by one workgroup (256 per round, a carry between
+// rounds); the list sizes and D[m] go to the head
+__global__ __launch_bounds__(256) void k_ab_scan_blocks(AliasTuple *blk, int chunks, int n, AliasHead *head, int64_t *D) {
+    __shared__ AliasTuple v[ab::kLanes];
+    __shared__ AliasTuple carry;
+    const int t = threadIdx.x;
+    if (t == 0) carry = AliasTuple{0, 0, 0, 0};
+    __syncthreads();
+    for (int c0 = 0; c0 < chunks; c0 += ab::kLanes) {
+        const int c = c0 + t;
+        const AliasTuple mine = c < chunks ? blk[c] : AliasTuple{0, 0, 0, 0};
+        const AliasTuple inc = scan256_lds(v, t, mine);
+        const AliasTuple base = carry;
+        if (c < chunks) {
+            AliasTuple ex = tuple_add(base, inc);
+            ex.d -= mine.d; ex.e -= mine.e; ex.nl -= mine.nl;
+            blk[c] = ex;
+        }
+        __syncthreads();
+        if (t == ab::kLanes - 1) carry = tuple_add(base, inc);
+        __syncthreads();
+    }
+    if (t == 0) {
+        head->m = carry.nl;
+        head->h = n - carry.nl;
+        D[carry.nl] = carry.d;
+    }
+}
+
+// stable partition: light k -> (bin, D_k), heavy j -> (bin, E_j)
+__global__ __launch_bounds__(256) void k_ab_scatter(int n, const AliasBin *out, const AliasTuple *blk, int64_t *D,
+                                                     int64_t *E, int *light, int *heavy) {
+    __shared__ AliasTuple v[ab::kLanes];
+    const int t = threadIdx.x;
+    const int base = blockIdx.x * ab::kChunk + t * ab::kPerLane;
+    int64_t f[ab::kPerLane];
+    AliasTuple mine{0, 0, 0, 0};
+    for (int k = 0; k < ab::kPerLane; ++k) {
+        const int i = base + k;
+        f[k] = ab::kOne;
+        if (i >= n) continue;
+        f[k] = ab::fixed(ab::scaled(out[i].p, n));
+        mine = tuple_add(mine, tuple_of(f[k]));
+    }
+    const AliasTuple inc = scan256_lds(v, t, mine);
+    AliasTuple run = tuple_add(blk[blockIdx.x], inc);
+    run.d -= mine.d; run.e -= mine.e; run.nl -= mine.nl;  // before this lane's items
+    for (int k = 0; k < ab::kPerLane; ++k) {
+        const int i = base + k;
+        if (i >= n) break;
+        if (f[k] < ab::kOne) {
+            light[run.nl] = i;
+            D[run.nl] = run.d;
+            run.d += ab::kOne - f[k];
+            ++run.nl;
+        } else {
+            const int j = i - run.nl;  // heavies before bin i
+            run.e += f[k] - ab::kOne;
+            heavy[j] = i;
+            E[j] = run.e;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ab_assign(int n, const AliasHead *head, const int64_t *D, const int64_t *E,
+                                                    const int *light, const int *heavy, AliasBin *out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const ab::Lists l{D, E, heavy, head->m, head->h};
+    float q;
+    int alias, i;
+    if (t < l.m) {
+        i = light[t];
+        ab::light_bin(l, t, ab::scaled(out[i].p, n), q, alias);
+    } else {
+        i = heavy[t - l.m];
+        ab::heavy_bin(l, t - l.m, q, alias);
+    }
+    out[i].q = q;
+    out[i].alias = alias;
+}
+
 }  // namespace
+
+hipError_t launch_tree_sum(const float *w, int n, const AliasScratch &s, AliasHead *head, hipStream_t st) {
+    const int chunks = (n + ab::kChunk - 1) / ab::kChunk;
+    hipLaunchKernelGGL(k_ab_sum1, dim3(chunks), dim3(256), 0, st, w, n, s.part);
+    hipLaunchKernelGGL(k_ab_sum2, dim3(1), dim3(256), 0, st, s.part, chunks, head);
+    return hipGetLastError();
+}
+
+hipError_t launch_alias_build(const float *w, int n, const AliasScratch &s, AliasHead *head, AliasBin *out,
+                              hipStream_t st) {
+    if (n < 1 || n > s.cap) return hipErrorInvalidValue;
+    const int chunks = (n + ab::kChunk - 1) / ab::kChunk;
+    if (hipError_t e = launch_tree_sum(w, n, s, head, st)) return e;
+    hipLaunchKernelGGL(k_ab_classify, dim3(chunks), dim3(256), 0, st, w, n, head, out, s.blk);
+    hipLaunchKernelGGL(k_ab_scan_blocks, dim3(1), dim3(256), 0, st, s.blk, chunks, n, head, s.D);
+    hipLaunchKernelGGL(k_ab_scatter, dim3(chunks), dim3(256), 0, st, n, out, s.blk, s.D, s.E, s.light, s.heavy);
+    hipLaunchKernelGGL(k_ab_assign, dim3((n + 255) / 256), dim3(256), 0, st, n, head, s.D, s.E, s.light, s.heavy, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_sky_lower_dev(float4 *sky, float *skyPdf, int skyW, int skyH, const AliasHead *upper, hipStream_t st) {
+    dim3 g((skyW + 63) / 64, (skyH / 2 + 3) / 4);
+    hipLaunchKernelGGL(k_sky_lower_dev, g, dim3(256), 0, st, sky, skyPdf, skyW, skyH, upper);
+    return hipGetLastError();
+}
 
 hipError_t launch_sky(const float *cfg90, const float *rad10, const float *solar, const float *limb, V3 sunDir,
                       float brightness, float4 *sky, float4 *sun, float *skyPdf, float *sunPdf, int skyW, int skyH,

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "vx_math.hpp"
+#include "alias_build.hpp"
 
 namespace vx {
 
@@ -50,6 +51,26 @@ struct TexBcInfo {
 };
 
 struct AliasBin { float q, p; int alias; };
+
+// the device alias build (alias_build.hpp, sky.hip): what one build leaves in device memory beside its
+// table, a scan element (deficit, excess and light count of a run of bins), and the scratch buffers
+struct AliasHead {
+    double sum;   // tree_sum of the weights
+    float fsum;   // (float)sum: the table's `sum`
+    int m, h;     // lights, heavies
+    int pad;
+};
+struct AliasTuple {
+    int64_t d, e;
+    int nl, pad;
+};
+struct AliasScratch {
+    int cap = 0;              // bins the buffers hold
+    double *part = nullptr;   // cap / 1024 + 1 chunk sums
+    AliasTuple *blk = nullptr;
+    int64_t *D = nullptr, *E = nullptr;  // cap + 1, cap
+    int *light = nullptr, *heavy = nullptr;
+};
 
 struct Reservoir { uint32_t lightData, uvData; float weightSum, targetPdf, M; };
 
@@ -265,6 +286,13 @@ hipError_t launch_sky(const float *cfg90, const float *rad10, const float *solar
                       float brightness, float4 *sky, float4 *sun, float *skyPdf, float *sunPdf, int skyW, int skyH,
                       int sunW, int sunH, hipStream_t st);
 hipError_t launch_sky_lower(float4 *sky, float *skyPdf, int skyW, int skyH, float sumUpper, hipStream_t st);
+// the lower hemisphere with the upper one's sum taken from upper->fsum on the device
+hipError_t launch_sky_lower_dev(float4 *sky, float *skyPdf, int skyW, int skyH, const AliasHead *upper, hipStream_t st);
+// head->sum / fsum = alias_build.hpp's tree_sum of w[0 .. n - 1] (n <= s.cap)
+hipError_t launch_tree_sum(const float *w, int n, const AliasScratch &s, AliasHead *head, hipStream_t st);
+// the alias table of w[0 .. n - 1] into out, its sum and list sizes into head
+hipError_t launch_alias_build(const float *w, int n, const AliasScratch &s, AliasHead *head, AliasBin *out,
+                              hipStream_t st);
 // a trace pass in two halves (trace.hip): the first reads nothing of the previous pass; the second
 // starts with the temporal reuse.  waitBeforeRestir: event the temporal-reuse kernel waits for (band
 // halo exchange), or null

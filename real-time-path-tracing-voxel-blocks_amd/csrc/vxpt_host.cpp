@@ -262,6 +262,15 @@ struct vxpt_ctx {
     float tabSky[540], tabSkyRad[60];
     DBuf<float> solar, limb;
     bool skyReady = false;
+    // device sky build (vxpt_set_sky_device) and the alias probe: the alias kernels' scratch, the
+    // builds' heads (0 upper-hemisphere sum, 1 sky table, 2 sun table, 3 probe) in device memory and
+    // the pinned host copy of the first three, and the event recorded behind a build (the front
+    // streams wait for it; the host waits for it before it reads the heads or the build's time)
+    AliasScratch aliasScratch;
+    AliasHead *skyHeads = nullptr, *hSkyHeads = nullptr;
+    hipEvent_t skyWritten = nullptr;
+    bool skyDevice = false;   // the tables are the device build's (hSkyAlias is filled on demand)
+    bool skyPending = false;  // heads and build time of the last device build not read yet
 
     // textures (materials.yaml `textures`, TextureManager): per block the albedo / normal /
     // roughness / metallic paths, the loaded RGBA8 mip chains and their table
@@ -702,6 +711,9 @@ bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, 
         case VXPT_BUF_OUTPUT: p = c->output; bytes = n * 16; return true;
         case VXPT_BUF_SKY: p = c->sky.p; bytes = 1024 * 512 * 16; return c->sky.p != nullptr;
         case VXPT_BUF_SUN: p = c->sun.p; bytes = 32 * 32 * 16; return c->sun.p != nullptr;
+        case VXPT_BUF_SKY_PDF: p = c->skyPdf.p; bytes = 1024 * 512 * 4; return !forWrite && c->skyPdf.p;
+        case VXPT_BUF_SUN_PDF: p = c->sunPdf.p; bytes = 32 * 32 * 4; return !forWrite && c->sunPdf.p;
+        case VXPT_BUF_SUN_ALIAS: p = c->sunAlias.p; bytes = 32 * 32 * sizeof(AliasBin); return !forWrite && c->sunAlias.p;
         case VXPT_BUF_VOXELS: p = c->voxels.p; bytes = (size_t)c->cx * c->cy * c->cz * 32768; return c->voxels.p != nullptr;
         case VXPT_BUF_OCTANT_TABLES: p = c->bdist.p; bytes = (size_t)8 * c->nBricks; return !forWrite && c->bdist.p;
         case VXPT_BUF_CELL_MASKS: p = c->cellMask.p; bytes = (size_t)c->nBricks * 8; return !forWrite && c->cellMask.p;
@@ -1985,6 +1997,8 @@ void vxpt_destroy(vxpt_ctx *c) {
     if (c->exDone) hipEventDestroy(c->exDone);
     for (hipEvent_t e : c->upEv)
         if (e) hipEventDestroy(e);
+    if (c->skyWritten) hipEventDestroy(c->skyWritten);
+    if (c->hSkyHeads) hipHostFree(c->hSkyHeads);
     delete c;
 }
 
@@ -2209,30 +2223,76 @@ int vxpt_upload_materials(vxpt_ctx *c, const vxpt_material *m, int n) {
     return VXPT_OK;
 }
 
-int vxpt_set_sky(vxpt_ctx *c, float tod, float axisAngle, float axisRotate, float brightness) {
-    if (!c) return VXPT_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->dev));
-    // sun direction (Sky.cu:363-368)
+namespace {
+
+constexpr int kSkyW = 1024, kSkyH = 512, kSunW = 32, kSunH = 32;
+
+// the sun direction (Sky.cu:363-368) into the context and the sky model's fitted state
+// (updateSkyState, Sky.cu:57-83, CPU fit); the maps and pdf planes on the first call
+int sky_state(vxpt_ctx *c, float tod, float axisAngle, float axisRotate, float cfg[90], float rad[10]) {
     V3 axis(1.0f, std::cos(axisAngle * kPiOver180), std::sin(axisAngle * kPiOver180));
     axis *= V3(std::sin(axisRotate * kPiOver180), 1.0f, std::cos(axisRotate * kPiOver180));
     axis = normalize(axis);
     const float angle = std::fmod(tod * kPi, kTwoPi);
     c->sunDir = normalized_c(q_rotate3(axis, angle, cross(V3(0, 1, 0), axis)));
-    // updateSkyState (Sky.cu:57-83), CPU fit
-    float cfg[90], rad[10];
     const float elevation = (kPi / 2.0f) - std::acos(c->sunDir.y);
     const float se = std::pow(elevation / (kPi / 2.0f), (1.0f / 3.0f));
     for (int ch = 0; ch < 10; ++ch) {
         for (int i = 0; i < 9; ++i) cfg[ch * 9 + i] = fit6(c->tabSky + ch * 54, se, i, 9);
         rad[ch] = fit6(c->tabSkyRad + ch * 6, se, 0, 1);
     }
-    const int sw = 1024, sh = 512, uw = 32, uh = 32;
+    const int sw = kSkyW, sh = kSkyH, uw = kSunW, uh = kSunH;
     if (!c->sky.p) {
         if (dalloc(c, c->sky.p, (size_t)sw * sh) || dalloc(c, c->sun.p, (size_t)uw * uh) ||
             dalloc(c, c->skyPdf.p, (size_t)sw * sh) || dalloc(c, c->sunPdf.p, (size_t)uw * uh))
             return VXPT_ERR_HIP;
         c->sky.n = (size_t)sw * sh; c->sun.n = (size_t)uw * uh;
     }
+    return 0;
+}
+
+// the alias kernels' scratch for n bins (at least the sky table's, so that the sky builds and the
+// probes up to that size share one allocation), the heads, and the build event: once per context
+int alias_scratch(vxpt_ctx *c, int n) {
+    if (!c->skyHeads) {
+        if (dalloc(c, c->skyHeads, 4)) return VXPT_ERR_HIP;
+        HIPCHK(c, hipHostMalloc((void **)&c->hSkyHeads, 3 * sizeof(AliasHead), hipHostMallocDefault));
+        HIPCHK(c, hipEventCreate(&c->skyWritten));
+    }
+    AliasScratch &s = c->aliasScratch;
+    if (s.cap >= n) return 0;
+    const size_t cap = (size_t)std::max(n, kSkyW * kSkyH);
+    if (dalloc(c, s.part, cap / ab::kChunk + 1) || dalloc(c, s.blk, cap / ab::kChunk + 1) || dalloc(c, s.D, cap + 1) ||
+        dalloc(c, s.E, cap) || dalloc(c, s.light, cap) || dalloc(c, s.heavy, cap))
+        return VXPT_ERR_HIP;
+    s.cap = (int)cap;
+    return 0;
+}
+
+// what a device sky build left for the host: the sun table's sum and the build's time (one wait for
+// the build's event; nothing to do after a host build)
+int sky_resolve(vxpt_ctx *c) {
+    if (!c->skyPending) return 0;
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipEventSynchronize(c->skyWritten));
+    c->sunLuminance = c->hSkyHeads[2].fsum;
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
+    c->timing.sky_ms = ms;
+    c->skyPending = false;
+    return 0;
+}
+
+}  // namespace
+
+int vxpt_set_sky(vxpt_ctx *c, float tod, float axisAngle, float axisRotate, float brightness) {
+    if (!c) return VXPT_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->dev));
+    float cfg[90], rad[10];
+    if (int r = sky_state(c, tod, axisAngle, axisRotate, cfg, rad)) return r;
+    const int sw = kSkyW, sh = kSkyH, uw = kSunW, uh = kSunH;
+    c->skyPending = false;
+    c->skyDevice = false;
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
     HIPCHK(c, launch_sky(cfg, rad, c->solar.p, c->limb.p, c->sunDir, brightness, c->sky.p, c->sun.p, c->skyPdf.p,
                          c->sunPdf.p, sw, sh, uw, uh, c->stream));
@@ -2259,6 +2319,68 @@ int vxpt_set_sky(vxpt_ctx *c, float tod, float axisAngle, float axisRotate, floa
     hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
     c->timing.sky_ms = ms;
     c->skyReady = true;
+    return VXPT_OK;
+}
+
+int vxpt_set_sky_device(vxpt_ctx *c, float tod, float axisAngle, float axisRotate, float brightness) {
+    if (!c) return VXPT_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->dev));
+    float cfg[90], rad[10];
+    if (int r = sky_state(c, tod, axisAngle, axisRotate, cfg, rad)) return r;
+    const int sw = kSkyW, sh = kSkyH, uw = kSunW, uh = kSunH;
+    if (int r = alias_scratch(c, sw * sh)) return r;
+    if (grow(c, c->skyAlias, (size_t)sw * sh) || grow(c, c->sunAlias, (size_t)uw * uh)) return VXPT_ERR_HIP;
+    // every earlier first half has finished before the context stream gets here: its second half, which
+    // waited for it, was enqueued on this stream
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    HIPCHK(c, launch_sky(cfg, rad, c->solar.p, c->limb.p, c->sunDir, brightness, c->sky.p, c->sun.p, c->skyPdf.p,
+                         c->sunPdf.p, sw, sh, uw, uh, c->stream));
+    const size_t half = (size_t)sw * (sh / 2);
+    HIPCHK(c, launch_tree_sum(c->skyPdf.p + half, (int)half, c->aliasScratch, c->skyHeads + 0, c->stream));
+    HIPCHK(c, launch_sky_lower_dev(c->sky.p, c->skyPdf.p, sw, sh, c->skyHeads + 0, c->stream));
+    HIPCHK(c, launch_alias_build(c->skyPdf.p, sw * sh, c->aliasScratch, c->skyHeads + 1, c->skyAlias.p, c->stream));
+    HIPCHK(c, launch_alias_build(c->sunPdf.p, uw * uh, c->aliasScratch, c->skyHeads + 2, c->sunAlias.p, c->stream));
+    // the one readback: the sun table's sum is a kernel argument of the post-process (sun_projection)
+    HIPCHK(c, hipMemcpyAsync(c->hSkyHeads, c->skyHeads, 3 * sizeof(AliasHead), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    // written: the passes' first halves read the maps and tables on the front streams
+    HIPCHK(c, hipEventRecord(c->skyWritten, c->stream));
+    for (hipStream_t fs : c->frontStreams)
+        if (fs) HIPCHK(c, hipStreamWaitEvent(fs, c->skyWritten, 0));
+    c->hSkyAlias.clear();
+    c->skyDevice = true;
+    c->skyPending = true;
+    c->skyReady = true;
+    return VXPT_OK;
+}
+
+int vxpt_alias_build_host(const float *w, int n, float *q, float *p, int32_t *alias, float *sum) {
+    return ab::build_host(w, n, q, p, alias, sum) ? VXPT_OK : VXPT_ERR_ARG;
+}
+
+int vxpt_alias_build(vxpt_ctx *c, const float *w, int n, float *q, float *p, int32_t *alias, float *sum) {
+    if (!c || !w || n < 1 || n > ab::kMaxN) return VXPT_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (int r = alias_scratch(c, n)) return r;
+    float *dw;
+    AliasBin *dout;
+    HIPCHK(c, hipMalloc(&dw, (size_t)n * 4));
+    HIPCHK(c, hipMalloc(&dout, (size_t)n * sizeof(AliasBin)));
+    std::vector<AliasBin> bins(n);
+    AliasHead head{};
+    HIPCHK(c, hipMemcpyAsync(dw, w, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_alias_build(dw, n, c->aliasScratch, c->skyHeads + 3, dout, c->stream));
+    HIPCHK(c, hipMemcpyAsync(bins.data(), dout, (size_t)n * sizeof(AliasBin), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&head, c->skyHeads + 3, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(dw);
+    hipFree(dout);
+    for (int i = 0; i < n; ++i) {
+        if (q) q[i] = bins[i].q;
+        if (p) p[i] = bins[i].p;
+        if (alias) alias[i] = bins[i].alias;
+    }
+    if (sum) *sum = head.fsum;
     return VXPT_OK;
 }
 
@@ -3336,6 +3458,7 @@ static void sun_projection(vxpt_ctx *c, int &on, int &px, int &py, float &u, flo
             py = std::min(std::max((int)(vv * c->H), 0), c->H - 1);
         }
     }
+    sky_resolve(c);  // a device-built sky's sun table sum
     lum = c->sunLuminance > 0.0f ? c->sunLuminance : 1.0f;
 }
 
@@ -3873,6 +3996,13 @@ int vxpt_upload(vxpt_ctx *c, int which, const void *host, size_t bytes) {
 
 int vxpt_get_sky_alias(vxpt_ctx *c, float *q, float *p, int32_t *alias, float *sunDir) {
     if (!c || !c->skyReady) return VXPT_ERR_STATE;
+    if (c->skyDevice && c->hSkyAlias.empty()) {  // a device-built table: read back on demand
+        HIPCHK(c, hipSetDevice(c->dev));
+        c->hSkyAlias.resize((size_t)kSkyW * kSkyH);
+        HIPCHK(c, hipMemcpyAsync(c->hSkyAlias.data(), c->skyAlias.p, c->hSkyAlias.size() * sizeof(AliasBin),
+                                 hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     for (size_t i = 0; i < c->hSkyAlias.size(); ++i) {
         if (q) q[i] = c->hSkyAlias[i].q;
         if (p) p[i] = c->hSkyAlias[i].p;
@@ -3921,7 +4051,18 @@ int vxpt_set_tuning(vxpt_ctx *c, const vxpt_tuning *t) {
 
 int vxpt_timings(vxpt_ctx *c, vxpt_timing *out) {
     if (!c || !out) return VXPT_ERR_ARG;
+    if (int r = sky_resolve(c)) return r;
     *out = c->timing;
+    return VXPT_OK;
+}
+
+int vxpt_device_memory(vxpt_ctx *c, uint64_t *free_bytes, uint64_t *total_bytes) {
+    if (!c) return VXPT_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->dev));
+    size_t f = 0, t = 0;
+    HIPCHK(c, hipMemGetInfo(&f, &t));
+    if (free_bytes) *free_bytes = f;
+    if (total_bytes) *total_bytes = t;
     return VXPT_OK;
 }
 

@@ -13,7 +13,8 @@
 // <prefix>_frames.csv of the library's timings; --render-scale S traces and post-processes at S times
 // the output size and brings the frame up to it with vxpt_upscale (--upscale, --sharpness) before it
 // is saved: the reference's interactive back end does the same (Backend::dynamicResolution), its
-// offline one does not.
+// offline one does not.  --time-of-day, --sun-axis-angle, --sun-axis-rotate and --sky-build set the sky
+// (the reference reads it from its settings; here the defaults are its values 0.25, 45, 0).
 // The scripted voxel-edit sequences (--test-sequence, --test-remove20, --test-remove-circle) follow
 // the reference's timing: a click set after frame N is picked at frame N+1 against the world as
 // edited so far (VoxelEngine::update, VoxelEngine.cu:906-975) and the geometry changes at frame
@@ -63,6 +64,11 @@ struct Options {
     float renderScale = 1.0f, sharpness = 1.0f;
     int upscaleMode = VXPT_UPSCALE_EASU_SHARPEN;
     int renderWidth = 0, renderHeight = 0;
+    // the sky: time of day (a T0:T1 range moves it linearly over the frames and sets it before each),
+    // the sun's axis, and where the tables are built (-1: device for a range, host otherwise)
+    float tod0 = 0.25f, tod1 = 0.25f, sunAxisAngle = 45.0f, sunAxisRotate = 0.0f;
+    bool todRange = false;
+    int skyBuild = -1;
 };
 
 const char *upscale_name(int mode) {
@@ -105,6 +111,14 @@ void usage(const char *argv0) {
               << "  --upscale <filter>     bicubic | easu | easu-sharp (default: easu-sharp): Catmull-Rom, the\n"
               << "                         edge-adaptive upsampler, or the upsampler and the sharpener\n"
               << "  --sharpness <f>        Strength of easu-sharp's sharpener, 0 <= f <= 1 (default: 1)\n"
+              << "  --time-of-day <t>      Time of day of the sky (default: 0.25), or T0:T1: the time moves linearly\n"
+              << "                         from T0 at the first frame to T1 at the last, the sky is rebuilt before\n"
+              << "                         each frame, and every frame is saved\n"
+              << "  --sun-axis-angle <deg> Tilt of the sun's axis (default: 45)\n"
+              << "  --sun-axis-rotate <deg> Rotation of the sun's axis (default: 0)\n"
+              << "  --sky-build <where>    host | device: Vose tables built on the host (waits for the GPU), or\n"
+              << "                         the parallel construction on the GPU (default: device for a T0:T1\n"
+              << "                         range, host otherwise)\n"
               << "  --help, -h             Show this help message\n";
 }
 
@@ -166,6 +180,28 @@ int parse(int argc, char **argv, Options &o) {
                 }
             }
         }
+        else if (a == "--time-of-day") {
+            if ((v = next("--time-of-day"))) {
+                const std::string t = v;
+                const size_t colon = t.find(':');
+                o.tod0 = o.tod1 = (float)std::atof(t.substr(0, colon).c_str());
+                o.todRange = colon != std::string::npos;
+                if (o.todRange) o.tod1 = (float)std::atof(t.substr(colon + 1).c_str());
+            }
+        }
+        else if (a == "--sun-axis-angle") { if ((v = next("--sun-axis-angle"))) { o.sunAxisAngle = (float)std::atof(v); } }
+        else if (a == "--sun-axis-rotate") { if ((v = next("--sun-axis-rotate"))) { o.sunAxisRotate = (float)std::atof(v); } }
+        else if (a == "--sky-build") {
+            if ((v = next("--sky-build"))) {
+                const std::string m = v;
+                if (m == "host") o.skyBuild = 0;
+                else if (m == "device") o.skyBuild = 1;
+                else {
+                    std::cerr << "--sky-build takes host or device\n";
+                    return -1;
+                }
+            }
+        }
         else if (a == "--test-sequence") o.testSequence = true;
         else if (a == "--test-remove20") o.removal20 = true;
         else if (a == "--test-remove-circle") o.removalCircle = true;
@@ -183,6 +219,11 @@ int parse(int argc, char **argv, Options &o) {
     if (!(o.renderScale >= 0.25f && o.renderScale <= 1.0f) || !(o.sharpness >= 0.0f && o.sharpness <= 1.0f)) {
         std::cerr << "render-scale must lie in [0.25, 1] and sharpness in [0, 1]\n";
         return -1;
+    }
+    if (o.skyBuild < 0) o.skyBuild = o.todRange ? 1 : 0;
+    if (o.todRange) {  // a day cycle is an animation: every frame is saved
+        o.savedFrames.clear();
+        for (int f = 1; f <= o.totalFrames; f++) o.savedFrames.push_back(f);
     }
     o.renderWidth = o.width;
     o.renderHeight = o.height;
@@ -238,7 +279,7 @@ std::string timestamp_now() {
 // PerformanceTracker::saveReport (PerformanceTracker.h:98-183): one run-summary line appended to the
 // report, the header first when the file is new; columns are per-frame averages in ms.  Here
 // PathTrace and Denoiser are the library's HIP-event times (the reference's are CPU launch times),
-// ScenePrep is 0 (the sky is built once by vxpt_set_sky, before the loop), RendererUpd the host's
+// ScenePrep is 0 (the sky is built before the loop, or per frame by --time-of-day T0:T1), RendererUpd the host's
 // voxel-engine update.
 bool append_run_summary(const std::string &path, const std::string &stamp, int w, int h,
                         const std::vector<FrameRecord> &perf, const std::string &comment) {
@@ -366,7 +407,10 @@ int main(int argc, char **argv) {
     if (vxpt_load_scene_camera(ctx, haveScene ? o.sceneFile.c_str() : nullptr, &cam) != VXPT_OK)
         return fail("loading the scene camera");
     if (vxpt_set_camera(ctx, &cam, &cam) != VXPT_OK) return fail("setting the camera");
-    if (vxpt_set_sky(ctx, 0.25f, 45.0f, 0.0f, 1.0f) != VXPT_OK) return fail("building the sky");
+    auto set_sky = [&](float tod) {
+        return (o.skyBuild ? vxpt_set_sky_device : vxpt_set_sky)(ctx, tod, o.sunAxisAngle, o.sunAxisRotate, 1.0f);
+    };
+    if (set_sky(o.tod0) != VXPT_OK) return fail("building the sky");
     std::cout << "Camera setup - Position: (" << cam.pos[0] << ", " << cam.pos[1] << ", " << cam.pos[2] << ")\n"
               << "Camera setup - Direction: (" << cam.dir[0] << ", " << cam.dir[1] << ", " << cam.dir[2] << ")\n"
               << "Camera setup - FOV: " << cam.fov_deg << " degrees\n"
@@ -460,6 +504,11 @@ int main(int argc, char **argv) {
             if (editPending)
                 std::cout << "EDIT: frame " << frameNumber << " block " << edit[3] << " at (" << edit[0] << ","
                           << edit[1] << "," << edit[2] << ")" << std::endl;
+        }
+
+        if (o.todRange && frame > 0) {  // frame 0's sky is the one set above
+            const float tod = o.tod0 + (o.tod1 - o.tod0) * ((float)frame / (float)(o.totalFrames - 1));
+            if (set_sky(tod) != VXPT_OK) return fail("building the sky");
         }
 
         const double updateMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

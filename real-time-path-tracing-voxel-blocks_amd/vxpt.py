@@ -25,7 +25,7 @@ BUF = dict(ILLUM=0, DEPTH=1, NORMAL_ROUGH=2, GEO_NORMAL_THIN=3, ALBEDO=4, MATERI
            PREV_HIST_LEN=20, OUTPUT=21, SKY=32, SUN=33, VOXELS=34, RES_EVEN=35, RES_ODD=36, WPOS=37, FRAME=38,
            OCTANT_TABLES=39, CELL_MASKS=40, BRICK_IDS=41, MACRO_MASKS=42, TEXELS=43, LIGHTS=44,
            LIGHT_ALIAS=45, BLOOM=46, TAP_RECORD=47, BOX_TABLES=48, CLAMP_DECISION=49, TEX_BLOCKS=50,
-           FRAME_UPSCALED=51)
+           FRAME_UPSCALED=51, SKY_PDF=52, SUN_PDF=53, SUN_ALIAS=54)
 # vxpt_upscale_mode
 UPSCALE_BICUBIC, UPSCALE_EASU, UPSCALE_EASU_SHARPEN = 0, 1, 2
 # vxpt_bc_format / vxpt_texture_flags
@@ -148,6 +148,9 @@ def load_library(path=LIB_PATH):
         "vxpt_upload_voxels": (I, [P, P, I, I, I]),
         "vxpt_upload_materials": (I, [P, ctypes.POINTER(Material), I]),
         "vxpt_set_sky": (I, [P, F, F, F, F]),
+        "vxpt_set_sky_device": (I, [P, F, F, F, F]),
+        "vxpt_alias_build_host": (I, [P, I, P, P, P, P]),
+        "vxpt_alias_build": (I, [P, P, I, P, P, P, P]),
         "vxpt_set_camera": (I, [P, ctypes.POINTER(Camera), ctypes.POINTER(Camera)]),
         "vxpt_get_camera": (I, [P, I, P]),
         "vxpt_set_camera_angles": (I, [P, P, F, F, F]),
@@ -191,6 +194,7 @@ def load_library(path=LIB_PATH):
         "vxpt_get_tuning": (I, [P, ctypes.POINTER(Tuning)]),
         "vxpt_set_tuning": (I, [P, ctypes.POINTER(Tuning)]),
         "vxpt_sync": (I, [P]),
+        "vxpt_device_memory": (I, [P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "vxpt_stream": (P, [P]),
         "vxpt_probe_rays": (I, [P, I, P, P, P, I]),
         "vxpt_probe_rng": (I, [P, I, P, P]),
@@ -312,8 +316,21 @@ class Renderer:
                   "vxpt_upload_voxels")
         self.chunks = tuple(chunks)
 
-    def set_sky(self, time_of_day=0.25, axis_angle=45.0, axis_rotate=0.0, brightness=1.0):
-        self._chk(self.lib.vxpt_set_sky(self.ctx, time_of_day, axis_angle, axis_rotate, brightness), "vxpt_set_sky")
+    def set_sky(self, time_of_day=0.25, axis_angle=45.0, axis_rotate=0.0, brightness=1.0, build="host"):
+        """build="host": vxpt_set_sky (Vose tables built on the host, waits); "device": vxpt_set_sky_device
+        (maps and tables built on the device, enqueued on the context stream, does not wait)."""
+        if build not in ("host", "device"):
+            raise VxptError("set_sky: build is 'host' or 'device'")
+        name = "vxpt_set_sky" if build == "host" else "vxpt_set_sky_device"
+        self._chk(getattr(self.lib, name)(self.ctx, time_of_day, axis_angle, axis_rotate, brightness), name)
+
+    def alias_build(self, weights):
+        """vxpt_alias_build: the device alias construction of the weights -> (q, p, alias, sum)."""
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        q, p, a, s = np.zeros(len(w), np.float32), np.zeros(len(w), np.float32), np.zeros(len(w), np.int32), ctypes.c_float()
+        self._chk(self.lib.vxpt_alias_build(self.ctx, _ptr(w), len(w), _ptr(q), _ptr(p), _ptr(a), ctypes.byref(s)),
+                  "vxpt_alias_build")
+        return q, p, a, np.float32(s.value)
 
     def set_camera(self, pos, direction, fov=90.0, prev=None):
         cur = Camera((ctypes.c_float * 3)(*pos), (ctypes.c_float * 3)(*direction), fov)
@@ -640,6 +657,12 @@ class Renderer:
     def sync(self):
         self._chk(self.lib.vxpt_sync(self.ctx), "vxpt_sync")
 
+    def device_memory(self):
+        """vxpt_device_memory: (free, total) bytes of the context's device."""
+        f, t = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self.lib.vxpt_device_memory(self.ctx, ctypes.byref(f), ctypes.byref(t)), "vxpt_device_memory")
+        return f.value, t.value
+
     # --- buffers ---
     def _shape(self, which):
         n = self.W * self.H
@@ -651,6 +674,12 @@ class Renderer:
             return np.zeros((512, 1024, 4), np.float32)
         if which == BUF["SUN"]:
             return np.zeros((32, 32, 4), np.float32)
+        if which == BUF["SKY_PDF"]:
+            return np.zeros((512, 1024), np.float32)
+        if which == BUF["SUN_PDF"]:
+            return np.zeros((32, 32), np.float32)
+        if which == BUF["SUN_ALIAS"]:
+            return np.zeros(32 * 32, ALIAS_DTYPE)
         if which == BUF["VOXELS"]:
             cx, cy, cz = self.chunks
             return np.zeros(cx * cy * cz * 32768, np.uint8)
@@ -723,6 +752,22 @@ class Renderer:
         out = np.zeros(len(q), np.float32)
         self._chk(self.lib.vxpt_probe_rng(self.ctx, len(q), _ptr(q), _ptr(out)), "vxpt_probe_rng")
         return out
+
+
+def alias_build_host(weights):
+    """vxpt_alias_build_host: the host twin of the device alias construction -> (q, p, alias, sum)."""
+    lib = load_library()
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    q, p, a, s = np.zeros(len(w), np.float32), np.zeros(len(w), np.float32), np.zeros(len(w), np.int32), ctypes.c_float()
+    rc = lib.vxpt_alias_build_host(_ptr(w), len(w), _ptr(q), _ptr(p), _ptr(a), ctypes.byref(s))
+    if rc != 0:
+        raise VxptError("vxpt_alias_build_host failed (%d)" % rc)
+    return q, p, a, np.float32(s.value)
+
+
+def alias_build(renderer, weights):
+    """vxpt_alias_build on the renderer's context (Renderer.alias_build)."""
+    return renderer.alias_build(weights)
 
 
 def render_offline(width, height, frames, spp=1, chunks=(2, 1, 2), height_scale=32.0, device=0):
