@@ -71,6 +71,8 @@ enum vxpt_buffer {
     VXPT_BUF_SKY_PDF = 52,       /* read-only: 1024*512 floats, the sky map's luminance (the sky table's weights) */
     VXPT_BUF_SUN_PDF = 53,       /* read-only: 32*32 floats, the sun map's luminance (the sun table's weights)    */
     VXPT_BUF_SUN_ALIAS = 54,     /* read-only: 32*32 x {f32 q, f32 p, i32 alias}, the sun map's alias table       */
+    VXPT_BUF_SKY_TOP = 55,       /* read-only: 4 x (bricks in z) x (bricks in x) u16, the walk's sky-exit table: per
+                                  * x / z direction quadrant and brick column, 1 + the highest cube row still ahead */
     VXPT_BUF_CLAMP_DECISION = 49 /* read-only parity hook (vxpt_debug_clamp_decisions): per pixel, a float
                                   * holding the last denoise's history-clamp decision bits -- 1: the x-only
                                   * Float3 compare cmin.x < centre.x (HistoryClamping.h:124), 2: cmax.x >
@@ -369,6 +371,32 @@ int vxpt_pick_block(vxpt_ctx *ctx, int32_t out[10]);
  * the traversal structures updated incrementally; the next trace pass's ReSTIR temporal visibility
  * sees no previous scene (OptixRenderer.cpp:916-919) */
 int vxpt_set_block(vxpt_ctx *ctx, int x, int y, int z, int block_id);
+/* n edits (x, y, z, block id each) applied in order -- a later edit of a cell wins.  Every buffer and the
+ * light-remap state end as after n vxpt_set_block calls; the voxel-table work is done once for the
+ * batch, while an edit of an instanced block (old or new id) refreshes the instances and lights where
+ * its vxpt_set_block would.  The whole batch is checked first: VXPT_ERR_ARG (a cell outside the world,
+ * an id outside 0..255) leaves the world untouched. */
+int vxpt_set_blocks(vxpt_ctx *ctx, const int32_t *xyz_id /* n x 4 */, int n);
+
+/* Where the walk's tables (brick-major ids, cell and macro masks, the 8 empty-cube and 8 empty-box
+ * tables, the sky-exit table) are built and edited.  HOST (the default): on the host, uploaded whole.
+ * DEVICE: by kernels from the chunk-major ids, which alone cross to the device; an edit is one
+ * scatter of the batch plus, after a brick turned occupied or empty, the prefix counts and the tables
+ * of the bricks behind it, enqueued on the context stream WITHOUT waiting for the GPU (the passes'
+ * first halves wait for it on their streams).  Both modes yield the same tables bit for bit.  Switching
+ * with a world loaded rebuilds its tables whole in the new mode; VXPT_ERR_ARG for another value.  Each
+ * context owns its world: call this, and the edits, on every member of a banded or linked set. */
+enum { VXPT_WORLD_BUILD_HOST = 0, VXPT_WORLD_BUILD_DEVICE = 1 };
+int vxpt_set_world_build(vxpt_ctx *ctx, int mode);
+/* GPU time of the kernels of the last device-mode build, table rebuild or edit batch (waits for them);
+ * VXPT_ERR_STATE before the first */
+int vxpt_world_build_ms(vxpt_ctx *ctx, float *ms);
+/* the device build's per-brick bodies run on the host, without a context or a GPU: every table of a
+ * world of cx x cy x cz chunks from its chunk-major ids.  Any output may be NULL; sizes as the
+ * VXPT_BUF_* of the same names (box caps 1..255). */
+int vxpt_world_tables_host(const uint8_t *ids, int cx, int cy, int cz, int box_cap, int box_cap_up, uint8_t *brick_ids,
+                           uint64_t *cell_masks, uint64_t *macro_masks, uint8_t *octant_tables, uint32_t *box_tables,
+                           uint16_t *sky_top);
 /* the click (:906-975): block_id 0 deletes the picked block, another id is placed in front of it;
  * out (may be NULL) = the pick */
 int vxpt_click_block(vxpt_ctx *ctx, int block_id, int32_t out[10]);

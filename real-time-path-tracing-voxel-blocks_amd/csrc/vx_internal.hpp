@@ -293,6 +293,39 @@ hipError_t launch_tree_sum(const float *w, int n, const AliasScratch &s, AliasHe
 // the alias table of w[0 .. n - 1] into out, its sum and list sizes into head
 hipError_t launch_alias_build(const float *w, int n, const AliasScratch &s, AliasHead *head, AliasBin *out,
                               hipStream_t st);
+// the world's DDA tables built and edited on the device (world.hip; bodies in world_build.hpp).
+// WbWorld: the chunk-major ids (input), the tables, and the build's own state -- the column tops as a
+// 32-bit plane (BX x BZ, the sky-exit table's input) and the prefix counts of occupied bricks
+struct WbWorld {
+    uint8_t *ids;
+    uint8_t *bricks;
+    uint64_t *macro, *cellMask;
+    uint8_t *bdist;
+    uint32_t *bbox;  // null: cube tables alone
+    uint16_t *skyTop;
+    uint32_t *colTop;
+    int *prefix;
+    int cx, cy, cz;
+    int cap, capUp;
+};
+// per octant, the inclusive brick box whose entries launch_wb_tables recomputes (x1 < x0: none)
+struct WbRanges {
+    struct { int x0, x1, y0, y1, z0, z1; } r[8];
+};
+// one scattered store of an edit batch: idx is an index into the array of the record's segment
+struct WbRec { uint64_t idx, val; };
+// segments of a batch's records, in this order: chunk-major id bytes, brick-major id bytes, whole cell
+// masks, whole macro words, raised column tops
+struct WbEditCounts { uint32_t n[5]; };
+// ids -> bricks, cellMask, macro, colTop (which it clears first)
+hipError_t launch_wb_occupancy(const WbWorld &w, hipStream_t st);
+// cellMask -> prefix (three axis passes, one serial scan per line)
+hipError_t launch_wb_prefix(const WbWorld &w, hipStream_t st);
+// prefix, cellMask -> bdist and (non-null) bbox over the ranges
+hipError_t launch_wb_tables(const WbWorld &w, const WbRanges &rg, hipStream_t st);
+hipError_t launch_wb_sky_top(const WbWorld &w, hipStream_t st);
+// rec: device-readable (pinned host) records, c.n[0] + .. + c.n[4] of them
+hipError_t launch_wb_edit(const WbWorld &w, const WbRec *rec, const WbEditCounts &c, hipStream_t st);
 // a trace pass in two halves (trace.hip): the first reads nothing of the previous pass; the second
 // starts with the temporal reuse.  waitBeforeRestir: event the temporal-reuse kernel waits for (band
 // halo exchange), or null

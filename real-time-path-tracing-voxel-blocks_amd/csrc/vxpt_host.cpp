@@ -35,6 +35,7 @@
 #include "prefilter.hpp"
 #include "upscale.hpp"
 #include "vx_internal.hpp"
+#include "world_build.hpp"
 
 using namespace vx;
 
@@ -249,6 +250,21 @@ struct vxpt_ctx {
     V3 nearPos{0.0f, 0.0f, 0.0f};
     float nearDist = 0.0f;
     int prevSceneEmpty = 0;     // the next trace pass's temporal visibility sees no previous scene
+    // tables built and edited on the device (vxpt_set_world_build; world.hip): the build's own device state
+    // (column tops as a 32-bit plane, prefix counts of occupied bricks); two pinned staging buffers for
+    // the edit batches' records, each reused only after the event behind the kernel that read it; the
+    // event recorded behind every build / edit (the front streams wait for it); and the events around
+    // the last build's / edit's kernels (vxpt_world_build_ms).  hOd, hBox and brickPrefix stay empty
+    int worldBuild = VXPT_WORLD_BUILD_HOST;
+    DBuf<uint32_t> dColTop;
+    DBuf<int> dPrefix;
+    WbRec *editStage[2] = {};
+    size_t editCap[2] = {};
+    hipEvent_t editDone[2] = {};
+    bool editUsed[2] = {};
+    int editNext = 0;
+    hipEvent_t worldWritten = nullptr, wbEv[2] = {};
+    bool wbTimed = false;
     MatDev mats[32] = {};  // by block id: 1..12 cubes (kernel arguments), 13..29 instanced meshes (meshMats)
     CamDev cam{}, prevCam{};
     float camYaw = 0, camPitch = 0;
@@ -727,6 +743,8 @@ bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, 
         case VXPT_BUF_TAP_RECORD: p = g.rec; bytes = n * 32; return !forWrite;
         case VXPT_BUF_CLAMP_DECISION: p = c->clampDbg; bytes = n * 4; return !forWrite && p;
         case VXPT_BUF_BOX_TABLES: p = c->bbox.p; bytes = (size_t)8 * c->nBricks * 4; return !forWrite && c->bbox.p;
+        case VXPT_BUF_SKY_TOP:
+            p = c->skyTop.p; bytes = (size_t)4 * (c->cx * 8) * (c->cz * 8) * 2; return !forWrite && c->skyTop.p && c->nBricks;
         case VXPT_BUF_LIGHT_ALIAS:
             p = c->lightAlias.p; bytes = (size_t)c->nLights * sizeof(AliasBin); return !forWrite && c->nLights;
         default: return false;
@@ -824,7 +842,9 @@ int upload_sky_top(vxpt_ctx *c) {
     return upload_vec(c, c->skyTop, c->hSkyTop.data(), c->hSkyTop.size());
 }
 
-int build_occupancy(vxpt_ctx *c, const uint8_t *ids) {
+// the host mirrors of a world (both build modes keep them: picking, vxpt_nearest_surface, chunk files
+// and the instance refresh read them, and an edit updates them in O(1))
+void build_mirrors(vxpt_ctx *c, const uint8_t *ids) {
     const int wx = c->cx * 32, wy = c->cy * 32, wz = c->cz * 32;
     const int mx = wx / 16, my = wy / 16, mz = wz / 16;
     c->hMacro.assign((size_t)mx * my * mz, 0ull);
@@ -855,6 +875,11 @@ int build_occupancy(vxpt_ctx *c, const uint8_t *ids) {
             }
     c->topValid = (tx * ty * tz <= 64) ? 1 : 0;
     refresh_top(c);
+}
+
+int build_occupancy(vxpt_ctx *c, const uint8_t *ids) {
+    const int wx = c->cx * 32, wy = c->cy * 32, wz = c->cz * 32;
+    build_mirrors(c, ids);
     if (int r = upload_sky_top(c)) return r;
     const int BX = wx / 4, BY = wy / 4, BZ = wz / 4;
     const size_t nB = (size_t)BX * BY * BZ;
@@ -930,6 +955,184 @@ int set_block(vxpt_ctx *c, int x, int y, int z, int id) {
     // gone, so the next pass's ReSTIR temporal visibility rays (closesthit.cu:736-755) miss
     c->prevSceneEmpty = 1;
     return 0;
+}
+
+// ---------------------------------------------------------------- tables on the device (world.hip)
+WbWorld wb_world(const vxpt_ctx *c) {
+    WbWorld w{};
+    w.ids = c->voxels.p;
+    w.bricks = c->bricks.p;
+    w.macro = c->macro.p;
+    w.cellMask = c->cellMask.p;
+    w.bdist = c->bdist.p;
+    w.bbox = c->useBoxes ? c->bbox.p : nullptr;
+    w.skyTop = c->skyTop.p;
+    w.colTop = c->dColTop.p;
+    w.prefix = c->dPrefix.p;
+    w.cx = c->cx; w.cy = c->cy; w.cz = c->cz;
+    w.cap = c->boxCap; w.capUp = c->boxCapUp;
+    return w;
+}
+WbRanges wb_whole(const vxpt_ctx *c) {
+    WbRanges rg;
+    for (auto &r : rg.r) r = {0, c->cx * 8 - 1, 0, c->cy * 8 - 1, 0, c->cz * 8 - 1};
+    return rg;
+}
+int wb_events(vxpt_ctx *c) {
+    if (c->worldWritten) return 0;
+    HIPCHK(c, hipEventCreateWithFlags(&c->worldWritten, hipEventDisableTiming));
+    for (auto &e : c->editDone) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto &e : c->wbEv) HIPCHK(c, hipEventCreate(&e));
+    return 0;
+}
+// behind a build's / edit's kernels on the context stream: every earlier first half has finished before
+// the stream got to them (its second half, which waited for it, was enqueued on this stream); the
+// passes' first halves read the tables on the front streams, so those wait here
+int wb_publish(vxpt_ctx *c) {
+    HIPCHK(c, hipEventRecord(c->wbEv[1], c->stream));
+    c->wbTimed = true;
+    HIPCHK(c, hipEventRecord(c->worldWritten, c->stream));
+    for (hipStream_t fs : c->frontStreams)
+        if (fs) HIPCHK(c, hipStreamWaitEvent(fs, c->worldWritten, 0));
+    return 0;
+}
+
+// every table of the uploaded ids (c->voxels) by the kernels; the host mirrors are built already
+int device_build(vxpt_ctx *c) {
+    const int BX = c->cx * 8, BY = c->cy * 8, BZ = c->cz * 8;
+    const size_t nB = (size_t)BX * BY * BZ;
+    if (nB > (size_t)INT_MAX) return fail(c, VXPT_ERR_ARG, "world too large");
+    if (int r = wb_events(c)) return r;
+    c->hOd = {};
+    c->hBox = {};
+    c->brickPrefix = BrickPrefix{};
+    c->hSkyTop = {};
+    if (grow(c, c->bricks, nB * 64) || grow(c, c->macro, nB / 64) || grow(c, c->cellMask, nB) ||
+        grow(c, c->bdist, 8 * nB) || (c->useBoxes && grow(c, c->bbox, 8 * nB)) ||
+        grow(c, c->skyTop, (size_t)4 * BX * BZ) || grow(c, c->dColTop, (size_t)BX * BZ) ||
+        grow(c, c->dPrefix, wb::prefix_size(BX, BY, BZ)))
+        return VXPT_ERR_HIP;
+    c->nBricks = (int)nB;
+    const WbWorld w = wb_world(c);
+    HIPCHK(c, hipEventRecord(c->wbEv[0], c->stream));
+    HIPCHK(c, launch_wb_occupancy(w, c->stream));
+    HIPCHK(c, launch_wb_prefix(w, c->stream));
+    HIPCHK(c, launch_wb_tables(w, wb_whole(c), c->stream));
+    HIPCHK(c, launch_wb_sky_top(w, c->stream));
+    if (int r = wb_publish(c)) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the cube and box tables of the current world, whole (a box switch or cap change)
+int device_tables(vxpt_ctx *c) {
+    if (c->useBoxes && grow(c, c->bbox, (size_t)8 * c->nBricks)) return VXPT_ERR_HIP;
+    HIPCHK(c, hipEventRecord(c->wbEv[0], c->stream));
+    HIPCHK(c, launch_wb_tables(wb_world(c), wb_whole(c), c->stream));
+    if (int r = wb_publish(c)) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// what a batch of edits touched, for its one scatter: the cells (chunk-major and brick-major byte
+// index; may repeat), the bricks whose cube mask changed with their occupancy before the batch, and
+// the raised columns
+struct EditBatch {
+    std::vector<std::pair<size_t, size_t>> cells;
+    std::map<size_t, bool> brickWas;
+    std::map<size_t, std::array<int, 3>> brickAt;
+    std::vector<size_t> cols;
+    bool any = false;
+};
+
+// set_block's changes of the host mirrors (the position is valid), recorded in the batch
+void edit_mirrors(vxpt_ctx *c, int x, int y, int z, int id, EditBatch &B) {
+    const int wx = c->cx * 32;
+    const size_t ci = (size_t)((x >> 5) + c->cx * ((z >> 5) + c->cz * (y >> 5))) * 32768 + (x & 31) +
+                      32 * ((z & 31) + 32 * (y & 31));
+    const int old = c->hIds[ci];
+    if (old == id) return;
+    B.any = true;
+    c->hIds[ci] = (uint8_t)id;
+    ++c->worldVersion;
+    const size_t b = brick_lin(c, x >> 2, y >> 2, z >> 2);
+    const int lc = (x & 3) + 4 * ((z & 3) + 4 * (y & 3));
+    c->hBricks[b * 64 + lc] = (uint8_t)id;
+    c->hNonAir[b] += (id != 0 ? 1 : 0) - (old != 0 ? 1 : 0);
+    B.cells.emplace_back(ci, b * 64 + lc);
+    if (is_cube(old) == is_cube(id)) return;
+    const uint64_t before = c->hCell[b];
+    if (B.brickWas.emplace(b, before != 0).second) B.brickAt[b] = {x >> 2, y >> 2, z >> 2};
+    c->hCell[b] = is_cube(id) ? (before | (1ull << lc)) : (before & ~(1ull << lc));
+    c->topCount[top_block(c, x, y, z)] += is_cube(id) ? 1 : -1;
+    const size_t col = (size_t)(z >> 2) * (wx >> 2) + (x >> 2);
+    if (is_cube(id) && c->colTop[col] < y + 1) {  // raised, never lowered: a bound
+        c->colTop[col] = (uint16_t)(y + 1);
+        B.cols.push_back(col);
+    }
+    if ((before != 0) != (c->hCell[b] != 0)) {
+        const size_t m = b / 64;
+        c->hMacro[m] = c->hCell[b] ? (c->hMacro[m] | (1ull << (b % 64))) : (c->hMacro[m] & ~(1ull << (b % 64)));
+    }
+}
+
+// the batch onto the device, without waiting for it: the records through a pinned staging buffer, one
+// scatter, and -- after an occupancy flip -- the prefix counts whole and the tables of, per octant, the
+// bricks behind the flipped ones (their bounding range: set_block's region for one brick)
+int edit_flush(vxpt_ctx *c, EditBatch &B) {
+    if (!B.any) return 0;
+    refresh_top(c);
+    c->prevSceneEmpty = 1;
+    std::sort(B.cells.begin(), B.cells.end());
+    B.cells.erase(std::unique(B.cells.begin(), B.cells.end()), B.cells.end());
+    std::sort(B.cols.begin(), B.cols.end());
+    B.cols.erase(std::unique(B.cols.begin(), B.cols.end()), B.cols.end());
+    const int BX = c->cx * 8, BY = c->cy * 8, BZ = c->cz * 8;
+    std::set<size_t> macros;
+    int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
+    for (const auto &kv : B.brickWas)
+        if (kv.second != (c->hCell[kv.first] != 0)) {
+            macros.insert(kv.first / 64);
+            const auto &at = B.brickAt[kv.first];
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = std::min(lo[a], at[a]);
+                hi[a] = std::max(hi[a], at[a]);
+            }
+        }
+    WbEditCounts cnt{{(uint32_t)B.cells.size(), (uint32_t)B.cells.size(), (uint32_t)B.brickWas.size(),
+                      (uint32_t)macros.size(), (uint32_t)B.cols.size()}};
+    const size_t total = 2 * B.cells.size() + B.brickWas.size() + macros.size() + B.cols.size();
+    const int k = c->editNext;
+    c->editNext ^= 1;
+    // the kernel that read this buffer two batches ago has normally long finished
+    if (c->editUsed[k]) HIPCHK(c, hipEventSynchronize(c->editDone[k]));
+    if (c->editCap[k] < total) {
+        if (c->editStage[k]) HIPCHK(c, hipHostFree(c->editStage[k]));
+        c->editStage[k] = nullptr;
+        c->editCap[k] = std::max<size_t>(1024, 2 * total);
+        HIPCHK(c, hipHostMalloc((void **)&c->editStage[k], c->editCap[k] * sizeof(WbRec), hipHostMallocDefault));
+    }
+    WbRec *r = c->editStage[k];
+    for (const auto &p : B.cells) *r++ = {p.first, c->hIds[p.first]};
+    for (const auto &p : B.cells) *r++ = {p.second, c->hBricks[p.second]};
+    for (const auto &kv : B.brickWas) *r++ = {kv.first, c->hCell[kv.first]};
+    for (size_t m : macros) *r++ = {m, c->hMacro[m]};
+    for (size_t col : B.cols) *r++ = {col, c->colTop[col]};
+    const WbWorld w = wb_world(c);
+    HIPCHK(c, hipEventRecord(c->wbEv[0], c->stream));
+    HIPCHK(c, launch_wb_edit(w, c->editStage[k], cnt, c->stream));
+    HIPCHK(c, hipEventRecord(c->editDone[k], c->stream));
+    c->editUsed[k] = true;
+    if (hi[0] >= 0) {
+        HIPCHK(c, launch_wb_prefix(w, c->stream));
+        WbRanges rg;
+        for (int oct = 0; oct < 8; ++oct)
+            rg.r[oct] = {(oct & 1) ? 0 : lo[0], (oct & 1) ? hi[0] : BX - 1, (oct & 2) ? 0 : lo[1],
+                         (oct & 2) ? hi[1] : BY - 1, (oct & 4) ? 0 : lo[2], (oct & 4) ? hi[2] : BZ - 1};
+        HIPCHK(c, launch_wb_tables(w, rg, c->stream));
+    }
+    if (!B.cols.empty()) HIPCHK(c, launch_wb_sky_top(w, c->stream));
+    return wb_publish(c);
 }
 
 }  // namespace
@@ -1999,6 +2202,10 @@ void vxpt_destroy(vxpt_ctx *c) {
         if (e) hipEventDestroy(e);
     if (c->skyWritten) hipEventDestroy(c->skyWritten);
     if (c->hSkyHeads) hipHostFree(c->hSkyHeads);
+    for (hipEvent_t e : {c->worldWritten, c->editDone[0], c->editDone[1], c->wbEv[0], c->wbEv[1]})
+        if (e) hipEventDestroy(e);
+    for (WbRec *p : c->editStage)
+        if (p) hipHostFree(p);
     delete c;
 }
 
@@ -2202,7 +2409,12 @@ int vxpt_upload_voxels(vxpt_ctx *c, const uint8_t *ids, int cxn, int cyn, int cz
     c->hIds.assign(ids, ids + n);
     ++c->worldVersion;
     if (int r = upload_vec(c, c->voxels, c->hIds.data(), n)) return r;
-    if (int r = build_occupancy(c, c->hIds.data())) return r;
+    if (c->worldBuild == VXPT_WORLD_BUILD_DEVICE) {  // only the chunk-major ids cross to the device
+        build_mirrors(c, c->hIds.data());
+        if (int r = device_build(c)) return r;
+    } else if (int r = build_occupancy(c, c->hIds.data())) {
+        return r;
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return refresh_instances(c, true, true);
 }
@@ -3037,16 +3249,8 @@ int vxpt_pick_block(vxpt_ctx *c, int32_t out[10]) {
     return VXPT_OK;
 }
 
-int vxpt_set_block(vxpt_ctx *c, int x, int y, int z, int block_id) {
-    if (!c) return VXPT_ERR_ARG;
-    if (c->hIds.empty()) return fail(c, VXPT_ERR_STATE, "no voxels uploaded");
-    HIPCHK(c, hipSetDevice(c->dev));
-    int old = 0;
-    if (x >= 0 && y >= 0 && z >= 0 && x < c->cx * 32 && y < c->cy * 32 && z < c->cz * 32) {
-        const size_t ch = (size_t)(x >> 5) + (size_t)c->cx * ((z >> 5) + (size_t)c->cz * (y >> 5));
-        old = c->hIds[ch * 32768 + (x & 31) + 32 * ((z & 31) + 32 * (y & 31))];
-    }
-    if (int r = set_block(c, x, y, z, block_id)) return r;
+// the instance / light side of one edit (old id -> block_id at a valid cell), after the grid changed
+static int edit_instances(vxpt_ctx *c, int x, int y, int z, int old, int block_id) {
     // the instance set only changes with an instanced block
     const auto inst = [&](int id) { return id > 0 && id < kBlockTypes && c->blocks[id].instanced; };
     if (!inst(old) && !inst(block_id)) return VXPT_OK;
@@ -3066,6 +3270,90 @@ int vxpt_set_block(vxpt_ctx *c, int x, int y, int z, int block_id) {
     if (ln >= 0) c->lightState.changed.insert(instance_id(c, ln, x, y, z));
     if (lo >= 0 || ln >= 0) c->lightState.incremental = true;
     return refresh_instances(c, lo >= 0 || ln >= 0, false);
+}
+
+static int id_at(const vxpt_ctx *c, int x, int y, int z) {
+    const size_t ch = (size_t)(x >> 5) + (size_t)c->cx * ((z >> 5) + (size_t)c->cz * (y >> 5));
+    return c->hIds[ch * 32768 + (x & 31) + 32 * ((z & 31) + 32 * (y & 31))];
+}
+
+int vxpt_set_block(vxpt_ctx *c, int x, int y, int z, int block_id) {
+    if (!c) return VXPT_ERR_ARG;
+    if (c->hIds.empty()) return fail(c, VXPT_ERR_STATE, "no voxels uploaded");
+    if (c->worldBuild == VXPT_WORLD_BUILD_DEVICE) {  // a batch of one
+        const int32_t e[4] = {x, y, z, block_id};
+        return vxpt_set_blocks(c, e, 1);
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    int old = 0;
+    if (x >= 0 && y >= 0 && z >= 0 && x < c->cx * 32 && y < c->cy * 32 && z < c->cz * 32) old = id_at(c, x, y, z);
+    if (int r = set_block(c, x, y, z, block_id)) return r;
+    return edit_instances(c, x, y, z, old, block_id);
+}
+
+int vxpt_set_blocks(vxpt_ctx *c, const int32_t *e, int n) {
+    if (!c || n < 0 || (n > 0 && !e)) return VXPT_ERR_ARG;
+    if (c->hIds.empty()) return fail(c, VXPT_ERR_STATE, "no voxels uploaded");
+    for (int i = 0; i < n; ++i) {  // the whole batch before anything changes
+        const int32_t *q = e + 4 * (size_t)i;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[0] >= c->cx * 32 || q[1] >= c->cy * 32 || q[2] >= c->cz * 32 ||
+            q[3] < 0 || q[3] > 255)
+            return fail(c, VXPT_ERR_ARG, "block position or id out of range");
+    }
+    if (c->worldBuild != VXPT_WORLD_BUILD_DEVICE) {
+        for (int i = 0; i < n; ++i)
+            if (int r = vxpt_set_block(c, e[4 * (size_t)i], e[4 * (size_t)i + 1], e[4 * (size_t)i + 2], e[4 * (size_t)i + 3]))
+                return r;
+        return VXPT_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    EditBatch B;
+    int rc = VXPT_OK;
+    for (int i = 0; i < n && rc == VXPT_OK; ++i) {
+        const int32_t *q = e + 4 * (size_t)i;
+        const int old = id_at(c, q[0], q[1], q[2]);
+        edit_mirrors(c, q[0], q[1], q[2], q[3], B);
+        rc = edit_instances(c, q[0], q[1], q[2], old, q[3]);
+    }
+    if (int r = edit_flush(c, B)) return r;
+    return rc;
+}
+
+int vxpt_set_world_build(vxpt_ctx *c, int mode) {
+    if (!c || (mode != VXPT_WORLD_BUILD_HOST && mode != VXPT_WORLD_BUILD_DEVICE)) return VXPT_ERR_ARG;
+    if (mode == c->worldBuild) return VXPT_OK;
+    HIPCHK(c, hipSetDevice(c->dev));
+    for (hipStream_t fs : c->frontStreams) HIPCHK(c, hipStreamSynchronize(fs));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->worldBuild = mode;
+    if (c->hIds.empty()) return VXPT_OK;
+    // the loaded world's tables, rebuilt whole in the new mode
+    ++c->worldVersion;
+    if (mode == VXPT_WORLD_BUILD_DEVICE) {
+        build_mirrors(c, c->hIds.data());
+        return device_build(c);
+    }
+    return build_occupancy(c, c->hIds.data());
+}
+
+int vxpt_world_build_ms(vxpt_ctx *c, float *ms) {
+    if (!c || !ms) return VXPT_ERR_ARG;
+    if (!c->wbTimed) return fail(c, VXPT_ERR_STATE, "no device build or edit yet");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipEventSynchronize(c->wbEv[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->wbEv[0], c->wbEv[1]));
+    return VXPT_OK;
+}
+
+int vxpt_world_tables_host(const uint8_t *ids, int cx, int cy, int cz, int box_cap, int box_cap_up, uint8_t *brick_ids,
+                           uint64_t *cell_masks, uint64_t *macro_masks, uint8_t *octant_tables, uint32_t *box_tables,
+                           uint16_t *sky_top) {
+    if (!ids || cx <= 0 || cy <= 0 || cz <= 0 || box_cap < 1 || box_cap > 255 || box_cap_up < 1 || box_cap_up > 255 ||
+        (size_t)cx * 8 * cy * 8 * cz * 8 > (size_t)INT_MAX)
+        return VXPT_ERR_ARG;
+    wb::tables_host(ids, cx, cy, cz, box_cap, box_cap_up, brick_ids, cell_masks, macro_masks, octant_tables, box_tables,
+                    sky_top);
+    return VXPT_OK;
 }
 
 // VoxelEngine::update's click (VoxelEngine.cu:906-975): block 0 deletes the picked block,
@@ -4038,7 +4326,9 @@ int vxpt_set_tuning(vxpt_ctx *c, const vxpt_tuning *t) {
     c->useBoxes = t->dda_boxes != 0;
     c->boxCap = t->box_cap;
     c->boxCapUp = t->box_cap_up;
-    if (tables && c->useBoxes && c->nBricks > 0) {  // the current world's box tables, rebuilt whole
+    if (tables && c->useBoxes && c->nBricks > 0 && c->worldBuild == VXPT_WORLD_BUILD_DEVICE) {
+        if (int r = device_tables(c)) return r;
+    } else if (tables && c->useBoxes && c->nBricks > 0) {  // the current world's box tables, rebuilt whole
         const int BX = c->cx * 8, BY = c->cy * 8, BZ = c->cz * 8;
         brick_prefix(c);
         c->hBox.assign((size_t)8 * c->nBricks, 0u);

@@ -69,6 +69,7 @@ struct Options {
     float tod0 = 0.25f, tod1 = 0.25f, sunAxisAngle = 45.0f, sunAxisRotate = 0.0f;
     bool todRange = false;
     int skyBuild = -1;
+    int worldBuild = VXPT_WORLD_BUILD_HOST;  // --world-build
 };
 
 const char *upscale_name(int mode) {
@@ -90,6 +91,7 @@ void usage(const char *argv0) {
               << "  --test-sequence        Enable scripted block placement test sequence\n"
               << "  --test-remove20        Enable scripted removal test (20 deletions)\n"
               << "  --test-remove-circle   Enable circular removal test (8 directions, 5 deletions each)\n"
+              << "  --world-build <m>      host (default) or device: where the walk's tables are built and edited\n"
               << "  --frames <int>         Number of frames to render (default: 64, use 1 for single frame)\n"
               << "  --spp <int>            Samples per pixel per frame (default: 1)\n"
               << "  --chunks <x> <y> <z>   World size in 32^3 chunks (default: 2 1 2)\n"
@@ -198,6 +200,17 @@ int parse(int argc, char **argv, Options &o) {
                 else if (m == "device") o.skyBuild = 1;
                 else {
                     std::cerr << "--sky-build takes host or device\n";
+                    return -1;
+                }
+            }
+        }
+        else if (a == "--world-build") {
+            if ((v = next("--world-build"))) {
+                const std::string m = v;
+                if (m == "host") o.worldBuild = VXPT_WORLD_BUILD_HOST;
+                else if (m == "device") o.worldBuild = VXPT_WORLD_BUILD_DEVICE;
+                else {
+                    std::cerr << "--world-build takes host or device\n";
                     return -1;
                 }
             }
@@ -384,6 +397,7 @@ int main(int argc, char **argv) {
         } else if (vxpt_load_textures(ctx, nullptr, &nTex) != VXPT_OK) return fail("loading textures");
         std::cout << "Textures loaded: " << nTex << (nTex ? "" : " (untextured materials)") << std::endl;
     }
+    if (vxpt_set_world_build(ctx, o.worldBuild) != VXPT_OK) return fail("setting the world build mode");
     if (vxpt_generate_terrain(ctx, o.chunks[0], o.chunks[1], o.chunks[2], 32.0f, 32.0f * o.chunks[0], 0) != VXPT_OK)
         return fail("generating terrain");
     // VoxelEngine::init (VoxelEngine.cu:809-816): the instanced meshes, their instances in the world and

@@ -25,7 +25,9 @@ BUF = dict(ILLUM=0, DEPTH=1, NORMAL_ROUGH=2, GEO_NORMAL_THIN=3, ALBEDO=4, MATERI
            PREV_HIST_LEN=20, OUTPUT=21, SKY=32, SUN=33, VOXELS=34, RES_EVEN=35, RES_ODD=36, WPOS=37, FRAME=38,
            OCTANT_TABLES=39, CELL_MASKS=40, BRICK_IDS=41, MACRO_MASKS=42, TEXELS=43, LIGHTS=44,
            LIGHT_ALIAS=45, BLOOM=46, TAP_RECORD=47, BOX_TABLES=48, CLAMP_DECISION=49, TEX_BLOCKS=50,
-           FRAME_UPSCALED=51, SKY_PDF=52, SUN_PDF=53, SUN_ALIAS=54)
+           FRAME_UPSCALED=51, SKY_PDF=52, SUN_PDF=53, SUN_ALIAS=54, SKY_TOP=55)
+# vxpt_set_world_build
+WORLD_BUILD = dict(host=0, device=1)
 # vxpt_upscale_mode
 UPSCALE_BICUBIC, UPSCALE_EASU, UPSCALE_EASU_SHARPEN = 0, 1, 2
 # vxpt_bc_format / vxpt_texture_flags
@@ -174,6 +176,10 @@ def load_library(path=LIB_PATH):
         "vxpt_mesh_probe": (I, [P, P, I, I, P, P]),
         "vxpt_mesh_occluded": (I, [P, P, I, P]),
         "vxpt_set_block": (I, [P, I, I, I, I]),
+        "vxpt_set_blocks": (I, [P, P, I]),
+        "vxpt_set_world_build": (I, [P, I]),
+        "vxpt_world_build_ms": (I, [P, ctypes.POINTER(F)]),
+        "vxpt_world_tables_host": (I, [P, I, I, I, I, I, P, P, P, P, P, P]),
         "vxpt_click_block": (I, [P, I, P]),
         "vxpt_save_world": (I, [P, ctypes.c_char_p, ctypes.c_char_p]),
         "vxpt_load_world": (I, [P, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Camera)]),
@@ -493,6 +499,26 @@ class Renderer:
     def set_block(self, x, y, z, block_id):
         self._chk(self.lib.vxpt_set_block(self.ctx, int(x), int(y), int(z), int(block_id)), "vxpt_set_block")
 
+    def set_blocks(self, xyz, ids):
+        """vxpt_set_blocks: the edits (xyz[i], ids[i]) in order, the voxel-table work once for the batch;
+        an invalid edit anywhere in it raises and leaves the world untouched."""
+        e = np.concatenate([np.asarray(xyz, np.int32).reshape(-1, 3), np.asarray(ids, np.int32).reshape(-1, 1)], 1)
+        e = np.ascontiguousarray(e)
+        self._chk(self.lib.vxpt_set_blocks(self.ctx, _ptr(e), len(e)), "vxpt_set_blocks")
+
+    def set_world_build(self, mode):
+        """"host" (the default) or "device": where the walk's tables are built and edited
+        (vxpt_set_world_build); a loaded world's tables are rebuilt whole in the new mode."""
+        if mode not in WORLD_BUILD:
+            raise VxptError("world build mode must be 'host' or 'device'")
+        self._chk(self.lib.vxpt_set_world_build(self.ctx, WORLD_BUILD[mode]), "vxpt_set_world_build")
+
+    def world_build_ms(self):
+        """GPU time of the last device-mode build / table rebuild / edit batch (waits for it)."""
+        ms = ctypes.c_float()
+        self._chk(self.lib.vxpt_world_build_ms(self.ctx, ctypes.byref(ms)), "vxpt_world_build_ms")
+        return ms.value
+
     def click_block(self, block_id):
         o = np.zeros(10, np.int32)
         self._chk(self.lib.vxpt_click_block(self.ctx, int(block_id), _ptr(o)), "vxpt_click_block")
@@ -680,6 +706,8 @@ class Renderer:
             return np.zeros((32, 32), np.float32)
         if which == BUF["SUN_ALIAS"]:
             return np.zeros(32 * 32, ALIAS_DTYPE)
+        if which == BUF["SKY_TOP"]:
+            return np.zeros((4, self.chunks[2] * 8, self.chunks[0] * 8), np.uint16)
         if which == BUF["VOXELS"]:
             cx, cy, cz = self.chunks
             return np.zeros(cx * cy * cz * 32768, np.uint8)
@@ -763,6 +791,26 @@ def alias_build_host(weights):
     if rc != 0:
         raise VxptError("vxpt_alias_build_host failed (%d)" % rc)
     return q, p, a, np.float32(s.value)
+
+
+def world_tables_host(ids, chunks, box_cap=32, box_cap_up=32):
+    """vxpt_world_tables_host: every walk table of a world from its chunk-major ids, by the device build's
+    bodies run on the host (no context, no GPU) -> dict keyed as Renderer.read's names."""
+    lib = load_library()
+    cx, cy, cz = (int(v) for v in chunks)
+    ids = np.ascontiguousarray(ids, np.uint8).reshape(-1)
+    if cx <= 0 or cy <= 0 or cz <= 0 or ids.size != cx * cy * cz * 32768:
+        raise VxptError("ids must hold 32768 bytes per chunk")
+    nb = cx * cy * cz * 512
+    out = dict(BRICK_IDS=np.zeros(nb * 64, np.uint8), CELL_MASKS=np.zeros(nb, np.uint64),
+               MACRO_MASKS=np.zeros(nb // 64, np.uint64), OCTANT_TABLES=np.zeros(8 * nb, np.uint8),
+               BOX_TABLES=np.zeros(8 * nb, np.uint32), SKY_TOP=np.zeros((4, cz * 8, cx * 8), np.uint16))
+    rc = lib.vxpt_world_tables_host(_ptr(ids), cx, cy, cz, int(box_cap), int(box_cap_up), _ptr(out["BRICK_IDS"]),
+                                    _ptr(out["CELL_MASKS"]), _ptr(out["MACRO_MASKS"]), _ptr(out["OCTANT_TABLES"]),
+                                    _ptr(out["BOX_TABLES"]), _ptr(out["SKY_TOP"]))
+    if rc != 0:
+        raise VxptError("vxpt_world_tables_host failed (%d)" % rc)
+    return out
 
 
 def alias_build(renderer, weights):
