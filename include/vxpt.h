@@ -73,6 +73,13 @@ enum vxpt_buffer {
     VXPT_BUF_SUN_ALIAS = 54,     /* read-only: 32*32 x {f32 q, f32 p, i32 alias}, the sun map's alias table       */
     VXPT_BUF_SKY_TOP = 55,       /* read-only: 4 x (bricks in z) x (bricks in x) u16, the walk's sky-exit table: per
                                   * x / z direction quadrant and brick column, 1 + the highest cube row still ahead */
+    VXPT_BUF_TLAS = 56,          /* read-only: the instances' TLAS, 2 * n - 1 nodes of 32 B {f32 lo[3], i32 left, f32 hi[3],
+                                  * i32 count} for n = vxpt_mesh_instance_count (host build: its own node count) */
+    VXPT_BUF_MESH_INST = 57,     /* read-only: n x 20 B {f32 cell[3], i32 block, i32 row}, the mesh instances in the
+                                  * TLAS's leaf order */
+    VXPT_BUF_LIGHT_WEIGHT = 58,  /* read-only: nLights floats, the light alias table's weights */
+    VXPT_BUF_MESH_ROW_LIGHT = 59, /* read-only: per instance row of vxpt_get_instances an i32, its first light record
+                                   * (-1: not an emissive instance) */
     VXPT_BUF_CLAMP_DECISION = 49 /* read-only parity hook (vxpt_debug_clamp_decisions): per pixel, a float
                                   * holding the last denoise's history-clamp decision bits -- 1: the x-only
                                   * Float3 compare cmin.x < centre.x (HistoryClamping.h:124), 2: cmax.x >
@@ -397,6 +404,36 @@ int vxpt_world_build_ms(vxpt_ctx *ctx, float *ms);
 int vxpt_world_tables_host(const uint8_t *ids, int cx, int cy, int cz, int box_cap, int box_cap_up, uint8_t *brick_ids,
                            uint64_t *cell_masks, uint64_t *macro_masks, uint8_t *octant_tables, uint32_t *box_tables,
                            uint16_t *sky_top);
+/* Where an instanced-block edit refreshes the TLAS and the light tables.  HOST (the default): the grid is
+ * scanned for the instances, the binned-SAH builder and Vose's alias construction run on the host, with
+ * host waits.  DEVICE: the instance set is kept under edits, the TLAS is a linear BVH (lbvh.hpp) and the
+ * light alias table the parallel construction (alias_build.hpp), both built by kernels enqueued on the
+ * context stream WITHOUT waiting for the GPU, once per vxpt_set_blocks batch; the passes' first halves
+ * wait for them on their streams.  Instance rows, light records, light mapping and remap equal HOST's bit
+ * for bit; the TLAS and the alias table are other valid ones.  A world with more than
+ * 1024 cells on an axis keeps the host TLAS builder (its uploads count as a host wait in the stats).  A loaded scene is rebuilt in the new mode; before
+ * vxpt_load_models the mode is kept and applied there.  VXPT_ERR_ARG for another value.  Each context owns
+ * its instances: call this on every member of a banded or linked set. */
+enum { VXPT_INSTANCE_BUILD_HOST = 0, VXPT_INSTANCE_BUILD_DEVICE = 1 };
+int vxpt_set_instance_build(vxpt_ctx *ctx, int mode);
+/* counters since the context was created: device-mode refreshes, TLAS builds, light-table builds (in host
+ * mode the same three count the host path's), and host waits (stream synchronisations) taken by the
+ * instance / light refresh inside vxpt_set_block / vxpt_set_blocks / vxpt_click_block */
+int vxpt_instance_build_stats(vxpt_ctx *ctx, uint32_t out[4]);
+/* GPU time of the last device-mode instance refresh on the context stream (waits for it): its copies from
+ * the staging block and its kernels (and, for a world that keeps the host TLAS builder, that builder's
+ * uploads); VXPT_ERR_STATE before one */
+int vxpt_instance_build_ms(vxpt_ctx *ctx, float *ms);
+/* instances that have a mesh: the TLAS's primitives (VXPT_BUF_MESH_INST rows); *n_nodes = the TLAS's nodes */
+int vxpt_mesh_instance_count(vxpt_ctx *ctx, int *n, int *n_nodes);
+/* the device TLAS builder's bodies run on the host, without a context or a GPU (lbvh.hpp): n boxes of 6
+ * floats and n keys below 2^35 (64-bit) -> 2n - 1 nodes (32 B each, the VXPT_BUF_TLAS layout) and order[k] =
+ * the primitive at leaf position k.  VXPT_ERR_ARG for a key out of range */
+int vxpt_lbvh_host(const float *boxes, const uint64_t *keys, int n, void *nodes, int32_t *order);
+/* an instance's key: the 30-bit Morton code of its cell (10 bits per axis) above its 5-bit object id */
+uint64_t vxpt_lbvh_key(int x, int y, int z, int object);
+/* 1 when a world of cx x cy x cz chunks builds its TLAS on the device in DEVICE mode (<= 1024 cells per axis) */
+int vxpt_lbvh_world_fits(int cx, int cy, int cz);
 /* the click (:906-975): block_id 0 deletes the picked block, another id is placed in front of it;
  * out (may be NULL) = the pick */
 int vxpt_click_block(vxpt_ctx *ctx, int block_id, int32_t out[10]);

@@ -27,6 +27,9 @@ schedule (vxpt_render_frame with a communicator, vxpt_render_frame_linked) does.
 own chain computes the history clamp's and the a-trous steps' out-of-band rows itself -- its ghost
 rows, tuning ghost_rows -- instead of exchanging after each of those passes; this host-driven schedule
 keeps one exchange per pass.  Both are the single-GPU render bit for bit.)
+
+Every band's renderer owns its world and its instances: set_world_build / set_instance_build and every
+edit go to each member of the set, in the same order, or the bands render different scenes.
 """
 import numpy as np
 

@@ -326,6 +326,24 @@ hipError_t launch_wb_tables(const WbWorld &w, const WbRanges &rg, hipStream_t st
 hipError_t launch_wb_sky_top(const WbWorld &w, hipStream_t st);
 // rec: device-readable (pinned host) records, c.n[0] + .. + c.n[4] of them
 hipError_t launch_wb_edit(const WbWorld &w, const WbRec *rec, const WbEditCounts &c, hipStream_t st);
+// the instances' TLAS as a linear BVH built on the device (instances.hip; bodies in lbvh.hpp): n mesh
+// instances, the m-th being instance row miRow[m] of meshRow (cell xyz, block id).  Scratch: packed
+// (npad = lbvh_padded(n) sort words), primBox (6 n), exact (6 (2n - 1)), slotInner (n), slotLeaf (n),
+// visits (n).  Out: nodes (2n - 1) and inst (n, in leaf order)
+struct LbvhDev {
+    int n, npad;
+    const int *miRow;
+    const int4 *meshRow;
+    const int2 *blasRoot;
+    const BvhNode *blas;
+    uint64_t *packed;
+    float *primBox, *exact;
+    int *slotInner, *slotLeaf, *visits;
+    BvhNode *nodes;
+    MeshInst *inst;
+};
+int lbvh_padded(int n);
+hipError_t launch_lbvh_build(const LbvhDev &a, hipStream_t st);
 // a trace pass in two halves (trace.hip): the first reads nothing of the previous pass; the second
 // starts with the temporal reuse.  waitBeforeRestir: event the temporal-reuse kernel waits for (band
 // halo exchange), or null

@@ -31,6 +31,7 @@
 #include "bcn.hpp"
 #include "box_tables.hpp"
 #include "bvh_build.hpp"
+#include "lbvh.hpp"
 #include "light_map.hpp"
 #include "prefilter.hpp"
 #include "upscale.hpp"
@@ -348,6 +349,29 @@ struct vxpt_ctx {
     DBuf<int> meshRowLight;
     DBuf<MatDev> meshMats;
     MatDev meshMatsUp[32] = {};  // what meshMats holds (uploaded when the materials change)
+    // instance refresh on the device (vxpt_set_instance_build; instances.hip): the instance set kept
+    // under edits (collect_instances' per-object map; valid while instSetValid), what an edit batch
+    // left to enqueue (instDirty: tables, instLightsDirty: light tables too, hRemap: the last light
+    // update's remap), the pinned staging pool (two buffers, more only while both are still being read;
+    // each reused only after the event behind its copies), the LBVH scratch, the light table's head
+    // (its fsum is the luminance sum, fetched on demand), the event behind a refresh (the front streams
+    // wait for it) and the events around its kernels.  ibStats: vxpt_instance_build_stats
+    int instBuild = VXPT_INSTANCE_BUILD_HOST;
+    std::map<int, std::map<unsigned, std::array<unsigned, 3>>> instSet;
+    bool instSetValid = false;
+    bool instDirty = false, instLightsDirty = false, instBatch = false;
+    std::vector<int> hRemap;
+    struct InstStage { char *p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; };
+    std::vector<InstStage> instStage;
+    DBuf<int> lbMiRow, lbSlotInner, lbSlotLeaf, lbVisits;
+    DBuf<uint64_t> lbPacked;
+    DBuf<float> lbPrimBox, lbExact;
+    int nTlasNodes = 0;
+    AliasHead *lightHead = nullptr;
+    bool lightLumOnDevice = false;
+    hipEvent_t instWritten = nullptr, ibEv[2] = {};
+    bool ibTimed = false;
+    uint32_t ibStats[4] = {};
     // vxpt_mesh_probe / vxpt_mesh_occluded scratch (grown to the largest call)
     DBuf<float> probeRays, probeOut;
     DBuf<int> probeIds;
@@ -495,6 +519,16 @@ int grow(vxpt_ctx *c, DBuf<T> &d, size_t n) {
     if (d.n >= n) return 0;
     if (dalloc(c, d.p, n)) return 1;
     d.n = n;
+    return 0;
+}
+
+// a buffer that a steady edit loop does not reallocate: grown to twice the need
+template <class T>
+int grow2(vxpt_ctx *c, DBuf<T> &d, size_t n) {
+    if (d.n >= n) return 0;
+    const size_t cap = std::max(n, 2 * d.n);
+    if (dalloc(c, d.p, cap)) return 1;
+    d.n = cap;
     return 0;
 }
 
@@ -747,6 +781,14 @@ bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, 
             p = c->skyTop.p; bytes = (size_t)4 * (c->cx * 8) * (c->cz * 8) * 2; return !forWrite && c->skyTop.p && c->nBricks;
         case VXPT_BUF_LIGHT_ALIAS:
             p = c->lightAlias.p; bytes = (size_t)c->nLights * sizeof(AliasBin); return !forWrite && c->nLights;
+        case VXPT_BUF_TLAS:
+            p = c->tlas.p; bytes = (size_t)c->nTlasNodes * sizeof(BvhNode); return !forWrite && c->nMeshInst > 0;
+        case VXPT_BUF_MESH_INST:
+            p = c->meshInst.p; bytes = (size_t)c->nMeshInst * sizeof(MeshInst); return !forWrite && c->nMeshInst > 0;
+        case VXPT_BUF_MESH_ROW_LIGHT:
+            p = c->meshRowLight.p; bytes = c->instances.size() / 5 * 4; return !forWrite && !c->instances.empty() && c->meshRowLight.p;
+        case VXPT_BUF_LIGHT_WEIGHT:
+            p = c->lightWeight.p; bytes = (size_t)c->nLights * 4; return !forWrite && c->nLights;
         default: return false;
     }
 }
@@ -2206,6 +2248,12 @@ void vxpt_destroy(vxpt_ctx *c) {
         if (e) hipEventDestroy(e);
     for (WbRec *p : c->editStage)
         if (p) hipHostFree(p);
+    for (hipEvent_t e : {c->instWritten, c->ibEv[0], c->ibEv[1]})
+        if (e) hipEventDestroy(e);
+    for (auto &s : c->instStage) {
+        if (s.done) hipEventDestroy(s.done);
+        if (s.p) hipHostFree(s.p);
+    }
     delete c;
 }
 
@@ -2400,6 +2448,7 @@ int vxpt_generate_terrain(vxpt_ctx *c, int cxn, int cyn, int czn, float heightSc
 }
 
 int refresh_instances(vxpt_ctx *c, bool lights, bool full);  // instanced meshes (+ lights), after the grid changed
+int refresh_instances_edit(vxpt_ctx *c, bool lights, bool full, const int *edit);  // the same after one edit
 
 int vxpt_upload_voxels(vxpt_ctx *c, const uint8_t *ids, int cxn, int cyn, int czn) {
     if (!c || !ids || cxn <= 0 || cyn <= 0 || czn <= 0) return VXPT_ERR_ARG;
@@ -2769,18 +2818,12 @@ uint32_t instance_id(const vxpt_ctx *c, unsigned obj, unsigned x, unsigned y, un
     return (unsigned)first + obj * W * W * W + (x + W * (z + W * y));
 }
 
-void collect_instances(vxpt_ctx *c) {
-    c->instances.clear();
-    if (c->hIds.empty()) return;
+// what each block id contributes to the instance set: its own object; a base block also the objects
+// of the lights paired with it; a paired light also its base's object
+int instance_contrib(const vxpt_ctx *c, std::vector<int> contrib[kBlockTypes]) {
     int first = kBlockTypes;
     for (int b = 0; b < kBlockTypes; ++b)
         if (c->blocks[b].instanced) { first = b; break; }
-    const unsigned W = (unsigned)c->cx * 32u, H = (unsigned)c->cy * 32u, D = (unsigned)c->cz * 32u;
-    std::map<int, std::map<unsigned, std::array<unsigned, 3>>> byObject;
-    auto inst_id = [&](unsigned obj, unsigned x, unsigned y, unsigned z) { return instance_id(c, obj, x, y, z); };
-    // one pass over the cells: what each block id contributes (its own object; a base block
-    // also the objects of the lights paired with it; a paired light also its base's object)
-    std::vector<int> contrib[kBlockTypes];
     for (int obj = first - 1; obj < kBlockTypes - 1; ++obj) {
         const int block = obj + 1, base = c->blocks[block].lightBase;
         contrib[block].push_back(obj);
@@ -2789,6 +2832,29 @@ void collect_instances(vxpt_ctx *c) {
             contrib[block].push_back(base - 1);
         }
     }
+    return first;
+}
+
+// the kept set as rows (objectId, instanceId, x, y, z), by object, then instance id
+void flatten_instances(vxpt_ctx *c) {
+    c->instances.clear();
+    for (const auto &o : c->instSet)
+        for (const auto &i : o.second)
+            c->instances.insert(c->instances.end(),
+                                {o.first, (int32_t)i.first, (int32_t)i.second[0], (int32_t)i.second[1], (int32_t)i.second[2]});
+}
+
+void collect_instances(vxpt_ctx *c) {
+    c->instances.clear();
+    c->instSet.clear();
+    c->instSetValid = false;
+    if (c->hIds.empty()) return;
+    const unsigned W = (unsigned)c->cx * 32u, H = (unsigned)c->cy * 32u, D = (unsigned)c->cz * 32u;
+    auto &byObject = c->instSet;
+    auto inst_id = [&](unsigned obj, unsigned x, unsigned y, unsigned z) { return instance_id(c, obj, x, y, z); };
+    // one pass over the cells
+    std::vector<int> contrib[kBlockTypes];
+    const int first = instance_contrib(c, contrib);
     for (unsigned x = 0; x < W; ++x)  // the reference's x, y, z order (last write wins)
         for (unsigned y = 0; y < H; ++y)
             for (unsigned z = 0; z < D; ++z) {
@@ -2797,25 +2863,84 @@ void collect_instances(vxpt_ctx *c) {
                 if (id < first || id >= kBlockTypes) continue;
                 for (int obj : contrib[id]) byObject[obj][inst_id(obj, x, y, z)] = {x, y, z};
             }
-    for (const auto &o : byObject)
-        for (const auto &i : o.second)
-            c->instances.insert(c->instances.end(),
-                                {o.first, (int32_t)i.first, (int32_t)i.second[0], (int32_t)i.second[1], (int32_t)i.second[2]});
+    flatten_instances(c);
+    // only device mode edits the set: host mode, which scans at every refresh, does not keep it
+    if (c->instBuild == VXPT_INSTANCE_BUILD_DEVICE) c->instSetValid = true;
+    else c->instSet.clear();
+}
+
+// One edit of the kept set (device instance mode), old id -> id at a valid cell, instead of the scan.
+// In a cubic world every coordinate is below the clamp of instance_id, so an (object, cell) pair has
+// its own id and a cell holds one block: the entry of each object the old id contributed goes, that
+// of each object the new id contributes comes.  In a non-cubic world two cells can share an id (the
+// scan's last write wins, which a local rule cannot reproduce): those worlds keep the scan.
+void edit_instance_set(vxpt_ctx *c, int x, int y, int z, int old, int id) {
+    if (!c->instSetValid || c->cx != c->cy || c->cx != c->cz) {
+        collect_instances(c);
+        return;
+    }
+    std::vector<int> contrib[kBlockTypes];
+    const int first = instance_contrib(c, contrib);
+    if (old >= first && old < kBlockTypes)
+        for (int obj : contrib[old]) {
+            const auto it = c->instSet.find(obj);
+            if (it == c->instSet.end()) continue;
+            it->second.erase(instance_id(c, (unsigned)obj, (unsigned)x, (unsigned)y, (unsigned)z));
+            if (it->second.empty()) c->instSet.erase(it);
+        }
+    if (id >= first && id < kBlockTypes)
+        for (int obj : contrib[id])
+            c->instSet[obj][instance_id(c, (unsigned)obj, (unsigned)x, (unsigned)y, (unsigned)z)] = {(unsigned)x, (unsigned)y, (unsigned)z};
+    flatten_instances(c);
 }
 
 // VoxelEngine::countLightTriangles / generateInstanceLights (VoxelEngine.cu:386-520) and
 // buildAliasTable (:150-192): the emissive objects in object order, each instance's
 // triangles in a row, one launch per object; then the weights' alias table (build_alias,
 // the same construction as the sky's) and their sum (accumulatedLocalLightLuminance).
-int build_lights(vxpt_ctx *c) {
+// the light table's layout from the instance rows: the light mapping and count, and (geometry) every
+// emissive mesh's triangles, instance cells and runs; returns the light count
+struct LightRun { size_t tri, cell; int nTri, nInst; V3 rad; };
+size_t light_layout(vxpt_ctx *c, bool geometry, std::vector<float> &tri, std::vector<int> &cells,
+                    std::vector<LightRun> &runs) {
     c->lightMap.clear();
     c->nLights = 0;
-    c->localLightLum = 0.0f;
     size_t total = 0;
     for (size_t k = 0; k < c->instances.size(); k += 5) {
         const auto &bd = c->blocks[c->instances[k] + 1];
         if (bd.emissive) total += (size_t)bd.triangles;
     }
+    if (total == 0) return 0;
+    for (size_t k = 0; k < c->instances.size();) {
+        const int obj = c->instances[k];
+        const auto &bd = c->blocks[obj + 1];
+        size_t e = k;
+        while (e < c->instances.size() && c->instances[e] == obj) e += 5;
+        if (bd.emissive && bd.triangles > 0) {
+            LightRun r{tri.size(), cells.size(), bd.triangles, (int)((e - k) / 5),
+                       V3(bd.emission[0], bd.emission[1], bd.emission[2])};
+            if (geometry) tri.insert(tri.end(), bd.pos.begin(), bd.pos.end());
+            for (size_t i = k; i < e; i += 5) {
+                if (geometry) cells.insert(cells.end(), {c->instances[i + 2], c->instances[i + 3], c->instances[i + 4]});
+                c->lightMap.insert(c->lightMap.end(),
+                                   {(uint32_t)c->instances[i + 1], (uint32_t)c->nLights, (uint32_t)bd.triangles});
+                c->nLights += (unsigned)bd.triangles;
+            }
+            runs.push_back(r);
+        }
+        k = e;
+    }
+    return total;
+}
+
+int build_lights(vxpt_ctx *c) {
+    c->localLightLum = 0.0f;
+    c->lightLumOnDevice = false;
+    // all emissive meshes' triangles and instance cells, uploaded once
+    std::vector<float> tri;
+    std::vector<int> cells;
+    std::vector<LightRun> runs;
+    const size_t total = light_layout(c, true, tri, cells, runs);
     if (total == 0) return VXPT_OK;
     if (c->lights.n < total) {
         if (dalloc(c, c->lights.p, total)) return VXPT_ERR_HIP;
@@ -2825,34 +2950,10 @@ int build_lights(vxpt_ctx *c) {
         if (dalloc(c, c->lightWeight.p, total)) return VXPT_ERR_HIP;
         c->lightWeight.n = total;
     }
-    // all emissive meshes' triangles and instance cells, uploaded once
-    std::vector<float> tri;
-    std::vector<int> cells;
-    struct Run { size_t tri, cell; int nTri, nInst; V3 rad; };
-    std::vector<Run> runs;
-    for (size_t k = 0; k < c->instances.size();) {
-        const int obj = c->instances[k];
-        const auto &bd = c->blocks[obj + 1];
-        size_t e = k;
-        while (e < c->instances.size() && c->instances[e] == obj) e += 5;
-        if (bd.emissive && bd.triangles > 0) {
-            Run r{tri.size(), cells.size(), bd.triangles, (int)((e - k) / 5),
-                  V3(bd.emission[0], bd.emission[1], bd.emission[2])};
-            tri.insert(tri.end(), bd.pos.begin(), bd.pos.end());
-            for (size_t i = k; i < e; i += 5) {
-                cells.insert(cells.end(), {c->instances[i + 2], c->instances[i + 3], c->instances[i + 4]});
-                c->lightMap.insert(c->lightMap.end(),
-                                   {(uint32_t)c->instances[i + 1], (uint32_t)c->nLights, (uint32_t)bd.triangles});
-                c->nLights += (unsigned)bd.triangles;
-            }
-            runs.push_back(r);
-        }
-        k = e;
-    }
     if (int r = upload_vec(c, c->lightTri, tri.data(), tri.size())) return r;
     if (int r = upload_vec(c, c->lightInst, cells.data(), cells.size())) return r;
     size_t off = 0;
-    for (const Run &r : runs) {
+    for (const LightRun &r : runs) {
         HIPCHK(c, launch_tri_lights(c->lightTri.p + r.tri, r.nTri, c->lightInst.p + r.cell, r.nInst, r.rad,
                                     c->lights.p + off, c->lightWeight.p + off, c->stream));
         off += (size_t)r.nTri * r.nInst;
@@ -2863,6 +2964,7 @@ int build_lights(vxpt_ctx *c) {
     const std::vector<AliasBin> bins = build_alias(w, c->localLightLum);
     if (int r = upload_vec(c, c->lightAlias, bins.data(), bins.size())) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ibStats[3] += 2;
     return VXPT_OK;
 }
 
@@ -2927,6 +3029,8 @@ int build_tlas(vxpt_ctx *c) {
     std::vector<MeshInst> sorted;
     for (int i : order) sorted.push_back(mi[i]);
     c->nMeshInst = (int)sorted.size();
+    c->nTlasNodes = c->nMeshInst ? (int)nodes.size() : 0;
+    ++c->ibStats[1];
     if (c->nMeshInst == 0) return VXPT_OK;
     if (int r = upload_vec(c, c->tlas, nodes.data(), nodes.size())) return r;
     return upload_vec(c, c->meshInst, sorted.data(), sorted.size());
@@ -2940,29 +3044,18 @@ int light_update(vxpt_ctx *c, unsigned prevN) {
     if (prevN > 0) {
         if (int r = upload_vec(c, c->lightRemap, remap.data(), remap.size())) return r;
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        ++c->ibStats[3];
     }
     c->prevNumLights = prevN;
     c->lightsDirty = 1;
     return VXPT_OK;
 }
 
-// lights: rebuild the light table as a light update (full: scene init / reload; otherwise of the
-// type the edits made it), or keep it (an edit of no emissive block, VoxelEngine.cu:1206, 1278)
-int refresh_instances(vxpt_ctx *c, bool lights, bool full) {
-    if (!c->modelsLoaded) return VXPT_OK;
-    collect_instances(c);
-    if (int r = build_tlas(c)) return r;
-    if (lights) {
-        if (full) c->lightState.incremental = false;
-        const unsigned prevN = c->nLights;
-        if (int r = build_lights(c)) return r;
-        if (int r = light_update(c, prevN)) return r;
-    }
-    // per instance row: cell + block, and its first light record (-1: not an emissive instance)
+// per instance row: cell + block, and its first light record (-1: not an emissive instance)
+void instance_rows(const vxpt_ctx *c, std::vector<int4> &rows, std::vector<int> &rowLight) {
     const size_t n = c->instances.size() / 5;
-    if (n == 0) return VXPT_OK;
-    std::vector<int4> rows(n);
-    std::vector<int> rowLight(n, -1);
+    rows.resize(n);
+    rowLight.assign(n, -1);
     std::map<uint32_t, int> firstLight;
     for (size_t k = 0; k < c->lightMap.size(); k += 3) firstLight[c->lightMap[k]] = (int)c->lightMap[k + 1];
     for (size_t i = 0; i < n; ++i) {
@@ -2972,6 +3065,194 @@ int refresh_instances(vxpt_ctx *c, bool lights, bool full) {
         const auto it = firstLight.find((uint32_t)r[1]);
         if (it != firstLight.end() && c->blocks[r[0] + 1].emissive) rowLight[i] = it->second;
     }
+}
+
+// device instance mode ------------------------------------------------------------------------------
+// a pinned staging buffer of `bytes` that no enqueued copy still reads: one of the pool whose event has
+// passed; while every one is busy the pool grows (to 8), and only then the host waits (counted)
+int inst_stage(vxpt_ctx *c, size_t bytes, int &slot) {
+    if (c->instStage.size() < 2) c->instStage.resize(2);
+    slot = -1;
+    for (size_t i = 0; i < c->instStage.size() && slot < 0; ++i)
+        if (!c->instStage[i].used || hipEventQuery(c->instStage[i].done) == hipSuccess) slot = (int)i;
+    (void)hipGetLastError();  // a pending event's hipErrorNotReady
+    if (slot < 0 && c->instStage.size() < 8) {
+        c->instStage.emplace_back();
+        slot = (int)c->instStage.size() - 1;
+    }
+    if (slot < 0) {
+        slot = 0;
+        HIPCHK(c, hipEventSynchronize(c->instStage[0].done));
+        ++c->ibStats[3];
+    }
+    auto &s = c->instStage[slot];
+    if (!s.done) HIPCHK(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (s.cap < bytes) {
+        if (s.p) HIPCHK(c, hipHostFree(s.p));
+        s.p = nullptr;
+        s.cap = std::max<size_t>(1 << 16, 2 * bytes);
+        HIPCHK(c, hipHostMalloc((void **)&s.p, s.cap, hipHostMallocDefault));
+    }
+    return 0;
+}
+
+// What the edits since the last flush left to do on the device, from the host state as it is now, without
+// waiting for the GPU: the rows, the TLAS (instances.hip) and -- after a light update -- the light
+// records, their alias table (sky.hip's parallel construction) and the remap.  Enqueued on the context
+// stream: every earlier first half has finished before the stream gets here (its second half, which
+// waited for it, was enqueued on this stream); the passes' first halves read the tables on the front
+// streams, so those wait for the event behind it.
+int inst_flush(vxpt_ctx *c) {
+    if (!c->instDirty) return VXPT_OK;
+    const bool lights = c->instLightsDirty;
+    if (lights && c->nLights > (unsigned)ab::kMaxN)  // the flags stay: the tables are not the state's
+        return fail(c, VXPT_ERR_STATE, "too many lights for the device alias build");
+    c->instDirty = c->instLightsDirty = false;
+    ++c->ibStats[0];
+    if (!c->instWritten) {
+        HIPCHK(c, hipEventCreateWithFlags(&c->instWritten, hipEventDisableTiming));
+        for (auto &e : c->ibEv) HIPCHK(c, hipEventCreate(&e));
+    }
+    std::vector<int4> rows;
+    std::vector<int> rowLight, miRow;
+    instance_rows(c, rows, rowLight);
+    const size_t n = rows.size();
+    for (size_t i = 0; i < n; ++i)
+        if (!c->hRoot.empty() && c->hRoot[rows[i].w].x >= 0) miRow.push_back((int)i);
+    const size_t nm = miRow.size();
+    const bool onDevice = lbvh::world_fits(c->cx * 32, c->cy * 32, c->cz * 32);
+    std::vector<float> tri;
+    std::vector<int> cells;
+    std::vector<LightRun> runs;
+    size_t total = 0;
+    if (lights) total = light_layout(c, true, tri, cells, runs);
+    const bool remap = lights && c->prevNumLights > 0 && !c->hRemap.empty();
+    // one staging block: rows, row lights, mesh rows, triangles, cells, remap (each 16-byte aligned)
+    const auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t oRows = 0, oRowLight = oRows + al(n * 16), oMi = oRowLight + al(n * 4), oTri = oMi + al(nm * 4),
+                 oCells = oTri + al(tri.size() * 4), oRemap = oCells + al(cells.size() * 4),
+                 bytes = oRemap + al(remap ? c->hRemap.size() * 4 : 0);
+    int slot = 0;
+    if (int r = inst_stage(c, std::max<size_t>(bytes, 16), slot)) return r;
+    char *st = c->instStage[slot].p;
+    if (n) {
+        std::memcpy(st + oRows, rows.data(), n * 16);
+        std::memcpy(st + oRowLight, rowLight.data(), n * 4);
+    }
+    if (nm) std::memcpy(st + oMi, miRow.data(), nm * 4);
+    if (!tri.empty()) std::memcpy(st + oTri, tri.data(), tri.size() * 4);
+    if (!cells.empty()) std::memcpy(st + oCells, cells.data(), cells.size() * 4);
+    if (remap) std::memcpy(st + oRemap, c->hRemap.data(), c->hRemap.size() * 4);
+    if (grow2(c, c->meshRow, n) || grow2(c, c->meshRowLight, n) || grow2(c, c->lbMiRow, nm)) return VXPT_ERR_HIP;
+    if (lights && total &&
+        (grow2(c, c->lights, total) || grow2(c, c->lightWeight, total) || grow2(c, c->lightAlias, total) ||
+         grow2(c, c->lightTri, tri.size()) || grow2(c, c->lightInst, cells.size())))
+        return VXPT_ERR_HIP;
+    if (remap && grow2(c, c->lightRemap, c->hRemap.size())) return VXPT_ERR_HIP;
+    if (lights && total) {
+        if (int r = alias_scratch(c, (int)total)) return r;
+        if (!c->lightHead && dalloc(c, c->lightHead, 1)) return VXPT_ERR_HIP;
+    }
+    HIPCHK(c, hipEventRecord(c->ibEv[0], c->stream));
+    const auto up = [&](void *dst, size_t off, size_t b) {
+        return b ? hipMemcpyAsync(dst, st + off, b, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, up(c->meshRow.p, oRows, n * 16));
+    HIPCHK(c, up(c->meshRowLight.p, oRowLight, n * 4));
+    HIPCHK(c, up(c->lbMiRow.p, oMi, nm * 4));
+    if (nm == 0) {
+        c->nMeshInst = 0;
+        c->nTlasNodes = 0;
+    } else if (onDevice) {
+        if (grow2(c, c->tlas, 2 * nm - 1) || grow2(c, c->meshInst, nm) || grow2(c, c->lbPacked, (size_t)lbvh_padded((int)nm)) ||
+            grow2(c, c->lbPrimBox, 6 * nm) || grow2(c, c->lbExact, 6 * (2 * nm - 1)) || grow2(c, c->lbSlotInner, nm) ||
+            grow2(c, c->lbSlotLeaf, nm) || grow2(c, c->lbVisits, nm))
+            return VXPT_ERR_HIP;
+        const LbvhDev a{(int)nm, lbvh_padded((int)nm), c->lbMiRow.p, c->meshRow.p, c->blasRoot.p, c->blas.p,
+                        c->lbPacked.p, c->lbPrimBox.p, c->lbExact.p, c->lbSlotInner.p, c->lbSlotLeaf.p, c->lbVisits.p,
+                        c->tlas.p, c->meshInst.p};
+        HIPCHK(c, launch_lbvh_build(a, c->stream));
+        c->nMeshInst = (int)nm;
+        c->nTlasNodes = 2 * (int)nm - 1;
+        ++c->ibStats[1];
+    } else {
+        // more than 1024 cells on an axis: the host builder, whose uploads from pageable memory hold the
+        // host until the copies are staged -- counted as a host wait
+        if (int r = build_tlas(c)) return r;
+        ++c->ibStats[3];
+    }
+    if (lights) {
+        ++c->ibStats[2];
+        c->localLightLum = 0.0f;
+        c->lightLumOnDevice = total > 0;
+        if (total) {
+            HIPCHK(c, up(c->lightTri.p, oTri, tri.size() * 4));
+            HIPCHK(c, up(c->lightInst.p, oCells, cells.size() * 4));
+            size_t off = 0;
+            for (const LightRun &r : runs) {
+                HIPCHK(c, launch_tri_lights(c->lightTri.p + r.tri, r.nTri, c->lightInst.p + r.cell, r.nInst, r.rad,
+                                            c->lights.p + off, c->lightWeight.p + off, c->stream));
+                off += (size_t)r.nTri * r.nInst;
+            }
+            HIPCHK(c, launch_alias_build(c->lightWeight.p, (int)total, c->aliasScratch, c->lightHead, c->lightAlias.p,
+                                         c->stream));
+        }
+        if (remap) HIPCHK(c, up(c->lightRemap.p, oRemap, c->hRemap.size() * 4));
+    }
+    HIPCHK(c, hipEventRecord(c->instStage[slot].done, c->stream));
+    c->instStage[slot].used = true;
+    HIPCHK(c, hipEventRecord(c->ibEv[1], c->stream));
+    c->ibTimed = true;
+    HIPCHK(c, hipEventRecord(c->instWritten, c->stream));
+    for (hipStream_t fs : c->frontStreams)
+        if (fs) HIPCHK(c, hipStreamWaitEvent(fs, c->instWritten, 0));
+    return VXPT_OK;
+}
+
+// the host side of a device-mode refresh, per edit exactly as in host mode: the instance rows (edit: x, y,
+// z, old id, new id -- the kept set; null: the scan), the light mapping, the light-update state and its
+// remap.  The device work is left to inst_flush: at once, or at the end of a vxpt_set_blocks batch
+int refresh_instances_device(vxpt_ctx *c, bool lights, bool full, const int *edit) {
+    if (edit) edit_instance_set(c, edit[0], edit[1], edit[2], edit[3], edit[4]);
+    else collect_instances(c);
+    if (lights) {
+        if (full) c->lightState.incremental = false;
+        const unsigned prevN = c->nLights;
+        std::vector<float> tri;
+        std::vector<int> cells;
+        std::vector<LightRun> runs;
+        light_layout(c, false, tri, cells, runs);
+        c->hRemap = light_id_map(c->lightState, c->lightMap, prevN, c->nLights);
+        c->prevNumLights = prevN;
+        c->lightsDirty = 1;
+        c->instLightsDirty = true;
+    }
+    c->instDirty = true;
+    return c->instBatch ? VXPT_OK : inst_flush(c);
+}
+
+// lights: rebuild the light table as a light update (full: scene init / reload; otherwise of the
+// type the edits made it), or keep it (an edit of no emissive block, VoxelEngine.cu:1206, 1278)
+int refresh_instances(vxpt_ctx *c, bool lights, bool full) { return refresh_instances_edit(c, lights, full, nullptr); }
+
+int refresh_instances_edit(vxpt_ctx *c, bool lights, bool full, const int *edit) {
+    if (!c->modelsLoaded) return VXPT_OK;
+    if (c->instBuild == VXPT_INSTANCE_BUILD_DEVICE) return refresh_instances_device(c, lights, full, edit);
+    ++c->ibStats[0];
+    collect_instances(c);
+    if (int r = build_tlas(c)) return r;
+    if (lights) {
+        if (full) c->lightState.incremental = false;
+        const unsigned prevN = c->nLights;
+        ++c->ibStats[2];
+        if (int r = build_lights(c)) return r;
+        if (int r = light_update(c, prevN)) return r;
+    }
+    const size_t n = c->instances.size() / 5;
+    if (n == 0) return VXPT_OK;
+    std::vector<int4> rows;
+    std::vector<int> rowLight;
+    instance_rows(c, rows, rowLight);
     if (int r = upload_vec(c, c->meshRow, rows.data(), rows.size())) return r;
     return upload_vec(c, c->meshRowLight, rowLight.data(), rowLight.size());
 }
@@ -3147,7 +3428,17 @@ int vxpt_get_lights(vxpt_ctx *c, uint32_t *mapping, int cap, int *n_mapped, uint
     if (n_mapped) *n_mapped = n;
     if (mapping) std::copy(c->lightMap.begin(), c->lightMap.begin() + (size_t)std::min(cap, n) * 3, mapping);
     if (n_lights) *n_lights = c->nLights;
-    if (local_luminance) *local_luminance = c->localLightLum;
+    if (local_luminance) {
+        if (c->lightLumOnDevice && c->nLights) {  // the device table's sum, fetched on demand
+            AliasHead head{};
+            HIPCHK(c, hipSetDevice(c->dev));
+            HIPCHK(c, hipMemcpyAsync(&head, c->lightHead, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            c->localLightLum = head.fsum;
+            c->lightLumOnDevice = false;
+        }
+        *local_luminance = c->localLightLum;
+    }
     return VXPT_OK;
 }
 
@@ -3269,7 +3560,8 @@ static int edit_instances(vxpt_ctx *c, int x, int y, int z, int old, int block_i
     if (lo >= 0) c->lightState.removed.insert(instance_id(c, lo, x, y, z));
     if (ln >= 0) c->lightState.changed.insert(instance_id(c, ln, x, y, z));
     if (lo >= 0 || ln >= 0) c->lightState.incremental = true;
-    return refresh_instances(c, lo >= 0 || ln >= 0, false);
+    const int edit[5] = {x, y, z, old, block_id};
+    return refresh_instances_edit(c, lo >= 0 || ln >= 0, false, edit);
 }
 
 static int id_at(const vxpt_ctx *c, int x, int y, int z) {
@@ -3300,23 +3592,78 @@ int vxpt_set_blocks(vxpt_ctx *c, const int32_t *e, int n) {
             q[3] < 0 || q[3] > 255)
             return fail(c, VXPT_ERR_ARG, "block position or id out of range");
     }
-    if (c->worldBuild != VXPT_WORLD_BUILD_DEVICE) {
-        for (int i = 0; i < n; ++i)
-            if (int r = vxpt_set_block(c, e[4 * (size_t)i], e[4 * (size_t)i + 1], e[4 * (size_t)i + 2], e[4 * (size_t)i + 3]))
-                return r;
-        return VXPT_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->dev));
-    EditBatch B;
+    // device instance mode: the edits' device work once, from the state after the last edit
+    const bool outer = c->instBatch;
+    c->instBatch = true;
     int rc = VXPT_OK;
+    if (c->worldBuild != VXPT_WORLD_BUILD_DEVICE) {
+        for (int i = 0; i < n && rc == VXPT_OK; ++i)
+            rc = vxpt_set_block(c, e[4 * (size_t)i], e[4 * (size_t)i + 1], e[4 * (size_t)i + 2], e[4 * (size_t)i + 3]);
+        c->instBatch = outer;
+        if (!outer)
+            if (int r = inst_flush(c)) return r;
+        return rc;
+    }
+    if (hipSetDevice(c->dev) != hipSuccess) {
+        c->instBatch = outer;
+        return fail(c, VXPT_ERR_HIP, "hipSetDevice");
+    }
+    EditBatch B;
     for (int i = 0; i < n && rc == VXPT_OK; ++i) {
         const int32_t *q = e + 4 * (size_t)i;
         const int old = id_at(c, q[0], q[1], q[2]);
         edit_mirrors(c, q[0], q[1], q[2], q[3], B);
         rc = edit_instances(c, q[0], q[1], q[2], old, q[3]);
     }
+    c->instBatch = outer;
     if (int r = edit_flush(c, B)) return r;
+    if (!outer)
+        if (int r = inst_flush(c)) return r;
     return rc;
+}
+
+int vxpt_set_instance_build(vxpt_ctx *c, int mode) {
+    if (!c || (mode != VXPT_INSTANCE_BUILD_HOST && mode != VXPT_INSTANCE_BUILD_DEVICE)) return VXPT_ERR_ARG;
+    if (mode == c->instBuild) return VXPT_OK;
+    HIPCHK(c, hipSetDevice(c->dev));
+    for (hipStream_t fs : c->frontStreams) HIPCHK(c, hipStreamSynchronize(fs));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->instBuild = mode;
+    // a loaded scene's tables, rebuilt whole in the new mode (before vxpt_load_models: applied there)
+    return refresh_instances(c, true, true);
+}
+
+int vxpt_instance_build_stats(vxpt_ctx *c, uint32_t out[4]) {
+    if (!c || !out) return VXPT_ERR_ARG;
+    std::copy(c->ibStats, c->ibStats + 4, out);
+    return VXPT_OK;
+}
+
+int vxpt_instance_build_ms(vxpt_ctx *c, float *ms) {
+    if (!c || !ms) return VXPT_ERR_ARG;
+    if (!c->ibTimed) return fail(c, VXPT_ERR_STATE, "no device instance refresh yet");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipEventSynchronize(c->ibEv[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->ibEv[0], c->ibEv[1]));
+    return VXPT_OK;
+}
+
+int vxpt_mesh_instance_count(vxpt_ctx *c, int *n, int *n_nodes) {
+    if (!c) return VXPT_ERR_ARG;
+    if (n) *n = c->nMeshInst;
+    if (n_nodes) *n_nodes = c->nTlasNodes;
+    return VXPT_OK;
+}
+
+int vxpt_lbvh_host(const float *boxes, const uint64_t *keys, int n, void *nodes, int32_t *order) {
+    return lbvh::build_host(boxes, keys, n, static_cast<BvhNode *>(nodes), order) ? VXPT_OK : VXPT_ERR_ARG;
+}
+
+uint64_t vxpt_lbvh_key(int x, int y, int z, int object) { return lbvh::instance_key(x, y, z, object); }
+
+int vxpt_lbvh_world_fits(int cx, int cy, int cz) {
+    return cx > 0 && cy > 0 && cz > 0 && cx <= 67108863 && cy <= 67108863 && cz <= 67108863 &&
+           lbvh::world_fits(cx * 32, cy * 32, cz * 32) ? 1 : 0;
 }
 
 int vxpt_set_world_build(vxpt_ctx *c, int mode) {

@@ -70,6 +70,10 @@ struct Options {
     bool todRange = false;
     int skyBuild = -1;
     int worldBuild = VXPT_WORLD_BUILD_HOST;  // --world-build
+    int instanceBuild = VXPT_INSTANCE_BUILD_HOST;  // --instance-build
+    // --load-world: the world (and, unless --scene is given, the camera) from a saved scene instead of the terrain
+    std::string worldYaml, worldChunks;
+    bool sceneGiven = false;
 };
 
 const char *upscale_name(int mode) {
@@ -92,6 +96,11 @@ void usage(const char *argv0) {
               << "  --test-remove20        Enable scripted removal test (20 deletions)\n"
               << "  --test-remove-circle   Enable circular removal test (8 directions, 5 deletions each)\n"
               << "  --world-build <m>      host (default) or device: where the walk's tables are built and edited\n"
+              << "  --instance-build <m>   host (default) or device: where an instanced-block edit refreshes the TLAS\n"
+              << "                         and the light tables\n"
+              << "  --load-world <yaml> <dir>  The world from a saved scene (vxpt_save_world: scene yaml and chunk\n"
+              << "                         directory) instead of the generated terrain; its camera too unless\n"
+              << "                         --scene is given\n"
               << "  --frames <int>         Number of frames to render (default: 64, use 1 for single frame)\n"
               << "  --spp <int>            Samples per pixel per frame (default: 1)\n"
               << "  --chunks <x> <y> <z>   World size in 32^3 chunks (default: 2 1 2)\n"
@@ -142,7 +151,7 @@ int parse(int argc, char **argv, Options &o) {
         if (a == "--width") { if ((v = next("--width"))) { o.width = std::atoi(v); } }
         else if (a == "--height") { if ((v = next("--height"))) { o.height = std::atoi(v); } }
         else if (a == "--output") { if ((v = next("--output"))) { o.outputPrefix = v; } }
-        else if (a == "--scene") { if ((v = next("--scene"))) { o.sceneFile = v; } }
+        else if (a == "--scene") { if ((v = next("--scene"))) { o.sceneFile = v; o.sceneGiven = true; } }
         else if (a == "--test-canonical" || a == "--test") o.testCanonical = true;
         else if (a == "--update-canonical") o.updateCanonical = true;
         else if (a == "--canonical-image") { if ((v = next("--canonical-image"))) { o.canonicalImagePath = v; } }
@@ -214,6 +223,23 @@ int parse(int argc, char **argv, Options &o) {
                     return -1;
                 }
             }
+        }
+        else if (a == "--instance-build") {
+            if ((v = next("--instance-build"))) {
+                const std::string m = v;
+                if (m == "host") o.instanceBuild = VXPT_INSTANCE_BUILD_HOST;
+                else if (m == "device") o.instanceBuild = VXPT_INSTANCE_BUILD_DEVICE;
+                else {
+                    std::cerr << "--instance-build takes host or device\n";
+                    return -1;
+                }
+            }
+        }
+        else if (a == "--load-world") {
+            if (!(v = next("--load-world"))) return -1;  // an extension flag: both values required
+            o.worldYaml = v;
+            if (!(v = next("--load-world"))) return -1;
+            o.worldChunks = v;
         }
         else if (a == "--test-sequence") o.testSequence = true;
         else if (a == "--test-remove20") o.removal20 = true;
@@ -398,7 +424,14 @@ int main(int argc, char **argv) {
         std::cout << "Textures loaded: " << nTex << (nTex ? "" : " (untextured materials)") << std::endl;
     }
     if (vxpt_set_world_build(ctx, o.worldBuild) != VXPT_OK) return fail("setting the world build mode");
-    if (vxpt_generate_terrain(ctx, o.chunks[0], o.chunks[1], o.chunks[2], 32.0f, 32.0f * o.chunks[0], 0) != VXPT_OK)
+    if (o.instanceBuild != VXPT_INSTANCE_BUILD_HOST && vxpt_set_instance_build(ctx, o.instanceBuild) != VXPT_OK)
+        return fail("setting the instance build mode");
+    vxpt_camera worldCam{};
+    if (!o.worldYaml.empty()) {
+        if (vxpt_load_world(ctx, o.worldYaml.c_str(), o.worldChunks.c_str(), &worldCam) != VXPT_OK)
+            return fail("loading the world");
+        std::cout << "World loaded: " << o.worldYaml << std::endl;
+    } else if (vxpt_generate_terrain(ctx, o.chunks[0], o.chunks[1], o.chunks[2], 32.0f, 32.0f * o.chunks[0], 0) != VXPT_OK)
         return fail("generating terrain");
     // VoxelEngine::init (VoxelEngine.cu:809-816): the instanced meshes, their instances in the world and
     // the light table (a full light update); block types whose OBJ file is missing stay empty
@@ -420,6 +453,7 @@ int main(int argc, char **argv) {
         std::cout << "Scene file not found: " << o.sceneFile << ", using defaults" << std::endl;
     if (vxpt_load_scene_camera(ctx, haveScene ? o.sceneFile.c_str() : nullptr, &cam) != VXPT_OK)
         return fail("loading the scene camera");
+    if (!o.worldYaml.empty() && !o.sceneGiven) cam = worldCam;
     if (vxpt_set_camera(ctx, &cam, &cam) != VXPT_OK) return fail("setting the camera");
     auto set_sky = [&](float tod) {
         return (o.skyBuild ? vxpt_set_sky_device : vxpt_set_sky)(ctx, tod, o.sunAxisAngle, o.sunAxisRotate, 1.0f);

@@ -25,9 +25,12 @@ BUF = dict(ILLUM=0, DEPTH=1, NORMAL_ROUGH=2, GEO_NORMAL_THIN=3, ALBEDO=4, MATERI
            PREV_HIST_LEN=20, OUTPUT=21, SKY=32, SUN=33, VOXELS=34, RES_EVEN=35, RES_ODD=36, WPOS=37, FRAME=38,
            OCTANT_TABLES=39, CELL_MASKS=40, BRICK_IDS=41, MACRO_MASKS=42, TEXELS=43, LIGHTS=44,
            LIGHT_ALIAS=45, BLOOM=46, TAP_RECORD=47, BOX_TABLES=48, CLAMP_DECISION=49, TEX_BLOCKS=50,
-           FRAME_UPSCALED=51, SKY_PDF=52, SUN_PDF=53, SUN_ALIAS=54, SKY_TOP=55)
+           FRAME_UPSCALED=51, SKY_PDF=52, SUN_PDF=53, SUN_ALIAS=54, SKY_TOP=55, TLAS=56, MESH_INST=57,
+           LIGHT_WEIGHT=58, MESH_ROW_LIGHT=59)
 # vxpt_set_world_build
 WORLD_BUILD = dict(host=0, device=1)
+# vxpt_set_instance_build
+INSTANCE_BUILD = dict(host=0, device=1)
 # vxpt_upscale_mode
 UPSCALE_BICUBIC, UPSCALE_EASU, UPSCALE_EASU_SHARPEN = 0, 1, 2
 # vxpt_bc_format / vxpt_texture_flags
@@ -37,6 +40,8 @@ FLOAT1_BUFS = {1, 5, 12, 13, 19, 20, 49}
 RESERVOIR_DTYPE = np.dtype([("lightData", "<u4"), ("uvData", "<u4"), ("weightSum", "<f4"), ("targetPdf", "<f4"),
                             ("M", "<f4")])
 ALIAS_DTYPE = np.dtype([("q", "<f4"), ("p", "<f4"), ("alias", "<i4")])
+BVH_NODE_DTYPE = np.dtype([("lo", "<f4", 3), ("left", "<i4"), ("hi", "<f4", 3), ("count", "<i4")])
+MESH_INST_DTYPE = np.dtype([("cell", "<f4", 3), ("block", "<i4"), ("row", "<i4")])
 TRACE_PRIMARY_ONLY = 1
 
 
@@ -180,6 +185,13 @@ def load_library(path=LIB_PATH):
         "vxpt_set_world_build": (I, [P, I]),
         "vxpt_world_build_ms": (I, [P, ctypes.POINTER(F)]),
         "vxpt_world_tables_host": (I, [P, I, I, I, I, I, P, P, P, P, P, P]),
+        "vxpt_set_instance_build": (I, [P, I]),
+        "vxpt_instance_build_stats": (I, [P, P]),
+        "vxpt_instance_build_ms": (I, [P, ctypes.POINTER(F)]),
+        "vxpt_mesh_instance_count": (I, [P, P, P]),
+        "vxpt_lbvh_host": (I, [P, P, I, P, P]),
+        "vxpt_lbvh_key": (ctypes.c_uint64, [I, I, I, I]),
+        "vxpt_lbvh_world_fits": (I, [I, I, I]),
         "vxpt_click_block": (I, [P, I, P]),
         "vxpt_save_world": (I, [P, ctypes.c_char_p, ctypes.c_char_p]),
         "vxpt_load_world": (I, [P, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Camera)]),
@@ -513,6 +525,57 @@ class Renderer:
             raise VxptError("world build mode must be 'host' or 'device'")
         self._chk(self.lib.vxpt_set_world_build(self.ctx, WORLD_BUILD[mode]), "vxpt_set_world_build")
 
+    def set_instance_build(self, mode):
+        """"host" (the default) or "device": where an instanced-block edit refreshes the TLAS and the
+        light tables (vxpt_set_instance_build); a loaded scene is rebuilt in the new mode."""
+        if mode not in INSTANCE_BUILD:
+            raise VxptError("instance build mode must be 'host' or 'device'")
+        self._chk(self.lib.vxpt_set_instance_build(self.ctx, INSTANCE_BUILD[mode]), "vxpt_set_instance_build")
+
+    def instance_build_stats(self):
+        """uint32 [4]: refreshes, TLAS builds, light-table builds, host waits taken inside edits."""
+        out = np.zeros(4, np.uint32)
+        self._chk(self.lib.vxpt_instance_build_stats(self.ctx, _ptr(out)), "vxpt_instance_build_stats")
+        return out
+
+    def instance_build_ms(self):
+        """GPU time of the last device-mode instance refresh (waits for it)."""
+        ms = ctypes.c_float()
+        self._chk(self.lib.vxpt_instance_build_ms(self.ctx, ctypes.byref(ms)), "vxpt_instance_build_ms")
+        return ms.value
+
+    def mesh_instance_count(self):
+        """(mesh instances, TLAS nodes)."""
+        n, m = ctypes.c_int(0), ctypes.c_int(0)
+        self._chk(self.lib.vxpt_mesh_instance_count(self.ctx, ctypes.byref(n), ctypes.byref(m)),
+                  "vxpt_mesh_instance_count")
+        return n.value, m.value
+
+    def tlas(self):
+        """(TLAS nodes [BVH_NODE_DTYPE], mesh instances in leaf order [MESH_INST_DTYPE])."""
+        n, m = self.mesh_instance_count()
+        nodes, inst = np.zeros(m, BVH_NODE_DTYPE), np.zeros(n, MESH_INST_DTYPE)
+        if n:
+            self._chk(self.lib.vxpt_readback(self.ctx, BUF["TLAS"], _ptr(nodes), nodes.nbytes), "vxpt_readback")
+            self._chk(self.lib.vxpt_readback(self.ctx, BUF["MESH_INST"], _ptr(inst), inst.nbytes), "vxpt_readback")
+        return nodes, inst
+
+    def mesh_row_light(self):
+        """int32 [instances]: each instance row's first light record, -1 for a row that emits nothing."""
+        out = np.zeros(len(self.instances()), np.int32)
+        if len(out):
+            self._chk(self.lib.vxpt_readback(self.ctx, BUF["MESH_ROW_LIGHT"], _ptr(out), out.nbytes), "vxpt_readback")
+        return out
+
+    def light_weights(self):
+        """float32 [nLights]: the light alias table's weights."""
+        nl = ctypes.c_uint32(0)
+        self._chk(self.lib.vxpt_get_lights(self.ctx, None, 0, None, ctypes.byref(nl), None), "vxpt_get_lights")
+        w = np.zeros(nl.value, np.float32)
+        if nl.value:
+            self._chk(self.lib.vxpt_readback(self.ctx, BUF["LIGHT_WEIGHT"], _ptr(w), w.nbytes), "vxpt_readback")
+        return w
+
     def world_build_ms(self):
         """GPU time of the last device-mode build / table rebuild / edit batch (waits for it)."""
         ms = ctypes.c_float()
@@ -791,6 +854,32 @@ def alias_build_host(weights):
     if rc != 0:
         raise VxptError("vxpt_alias_build_host failed (%d)" % rc)
     return q, p, a, np.float32(s.value)
+
+
+def lbvh_key(x, y, z, obj):
+    """vxpt_lbvh_key: an instance's 35-bit sort key (Morton code of the cell, then the object id)."""
+    return int(load_library().vxpt_lbvh_key(int(x), int(y), int(z), int(obj)))
+
+
+def lbvh_world_fits(chunks):
+    """vxpt_lbvh_world_fits: device mode builds this world's TLAS on the device (<= 1024 cells per axis)."""
+    return bool(load_library().vxpt_lbvh_world_fits(*(int(v) for v in chunks)))
+
+
+def lbvh_host(boxes, keys):
+    """vxpt_lbvh_host: the host twin of the device TLAS builder -> (nodes [2n - 1] BVH_NODE_DTYPE,
+    order int32 [n]: the primitive at each leaf position)."""
+    lib = load_library()
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    k = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+    if len(b) != len(k):
+        raise VxptError("one key per box")
+    n = len(k)
+    nodes, order = np.zeros(max(2 * n - 1, 0), BVH_NODE_DTYPE), np.zeros(n, np.int32)
+    rc = lib.vxpt_lbvh_host(_ptr(b), _ptr(k), n, _ptr(nodes), _ptr(order))
+    if rc != 0:
+        raise VxptError("vxpt_lbvh_host failed (%d)" % rc)
+    return nodes, order
 
 
 def world_tables_host(ids, chunks, box_cap=32, box_cap_up=32):
