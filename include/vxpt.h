@@ -303,8 +303,14 @@ int vxpt_texture_table(vxpt_ctx *ctx, int32_t *out, int cap, int *n_textures, in
 enum vxpt_bc_format { VXPT_BC4 = 4, VXPT_BC5 = 5, VXPT_BC7 = 7 };
 enum vxpt_texture_flags {
     VXPT_TEX_WRITE_CACHE = 1, /* write the levels this call encodes to cache_dir */
-    VXPT_TEX_EXPAND = 2       /* decode the blocks on the host into the RGBA8 texel buffer: the block
+    VXPT_TEX_EXPAND = 2,      /* decode the blocks on the host into the RGBA8 texel buffer: the block
                                * set's exact texels through the RGBA8 sampler, at 4x the bytes */
+    VXPT_TEX_ENCODE_SEARCH = 4 /* encode the levels that have no usable cache file with the search encoder
+                               * (vxpt_bc_encode_q quality 1) on the device: one launch per format for the
+                               * whole set.  Cached levels are still the files' bytes.  The blocks are read
+                               * back only where VXPT_TEX_WRITE_CACHE or VXPT_TEX_EXPAND needs them.  A cache
+                               * written by such a load is read verbatim by later loads, with or without
+                               * this bit.  Without the bit the call is what it was, byte for byte. */
 };
 /* vxpt_load_textures with every level stored as blocks: the same texture set, sorted-path ids,
  * material binding and mip chain; the format follows the PNG's channel count (:193-210).  A level
@@ -325,6 +331,21 @@ int vxpt_bc_decode(int format, const void *blocks, int n_blocks_x, int n_blocks_
  * mode 6 with endpoints on the block's colour-box diagonal, BC4 / BC5 max / min endpoints in the
  * 8-value mode.  It does not try to match the reference's encoder (NVTT). */
 int vxpt_bc_encode(int format, const uint8_t *rgba, int w, int h, void *blocks_out);
+/* vxpt_bc_encode at a quality, host only.  0: vxpt_bc_encode's bytes.  1: a search -- per block the
+ * candidate with the smallest summed squared error wins, a tie going to the earlier candidate, and
+ * the quality-0 block is the first candidate, so no block gets worse.  BC7: mode 6 with fitted and
+ * refined endpoints, modes 1 and 3 over the 64 two-subset partitions (blocks of alpha 255), modes 5
+ * and 7 (the others); BC4 / BC5: endpoint pairs near max / min, and the 6-value mode for blocks
+ * holding 0 or 255 (csrc/bcn_encode.hpp).  Integer arithmetic: the same bytes on every machine.
+ * VXPT_ERR_ARG for another quality or for sizes that are not positive multiples of 4. */
+int vxpt_bc_encode_q(int format, const uint8_t *rgba, int w, int h, int quality, void *blocks_out);
+/* the same through the device encoders (csrc/bcn_encode.hip): upload, one launch, read back.  The
+ * same bytes as vxpt_bc_encode_q. */
+int vxpt_bc_encode_device(vxpt_ctx *ctx, int format, const uint8_t *rgba, int w, int h, int quality, void *blocks_out);
+/* GPU time of the last device encode (vxpt_bc_encode_device, or a vxpt_load_textures_bc with
+ * VXPT_TEX_ENCODE_SEARCH that had levels to encode), from events on the context stream; waits for it.
+ * VXPT_ERR_STATE before the first one. */
+int vxpt_bc_encode_ms(vxpt_ctx *ctx, float *ms);
 /* the cache file of one level (TextureManager.cu:168-173, 271) */
 int vxpt_bc_cache_path(const char *cache_dir, const char *tex_path, int lod, char *out, int cap);
 /* one size x size level as the loader resolves it: cache file or encode (flags: VXPT_TEX_WRITE_CACHE) */

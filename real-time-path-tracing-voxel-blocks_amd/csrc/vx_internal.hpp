@@ -50,6 +50,15 @@ struct TexBcInfo {
     unsigned off[kMaxTexLevels];
 };
 
+// One 4x4 block for the device encoders (bcn_encode.hip): src = the first texel of the block's level in
+// the RGBA8 texel buffer, width = the level's width in texels, (bx, by) = the block in the level, dst =
+// the byte offset of its output in the block buffer (16-byte aligned; BC4: 8)
+struct BcEncJob {
+    uint32_t src, width;
+    uint16_t bx, by;
+    uint32_t dst;
+};
+
 struct AliasBin { float q, p; int alias; };
 
 // the device alias build (alias_build.hpp, sky.hip): what one build leaves in device memory beside its
@@ -355,6 +364,9 @@ hipError_t launch_probe_rng(const BlueNoiseDev &bn, int n, const int *q, float *
 // tex_lod of texture id for n (u, v, lod) triples -> n float4; blocks non-null: the block sampler
 hipError_t launch_probe_texture(const TexInfo *tex, const uchar4 *texels, const TexBcInfo *texBc, const uint8_t *blocks,
                                 int id, int n, const float *uvlod, float4 *out, hipStream_t st);
+// the n jobs' blocks of the format (bcn_decode.hpp: 4, 5, 7) at the quality (0 fast, 1 search), one launch
+hipError_t launch_bc_encode(int format, const uint32_t *texels, const BcEncJob *jobs, int n, int quality, uint8_t *out,
+                            hipStream_t st);
 
 struct DenoiseParamsDev {
     float maxAcc, maxFast, phiL, lobeAngleFraction, roughnessFraction, depthThreshold;

@@ -29,6 +29,7 @@
 
 #include "../../include/vxpt.h"
 #include "bcn.hpp"
+#include "bcn_decode.hpp"
 #include "box_tables.hpp"
 #include "bvh_build.hpp"
 #include "lbvh.hpp"
@@ -304,6 +305,9 @@ struct vxpt_ctx {
     std::vector<TexBcInfo> hTexBc;
     size_t nTexBlockBytes = 0;
     bool texBcOn = false;
+    // the events around the last device encode's kernels (vxpt_bc_encode_ms), created on first use
+    hipEvent_t bcEv[2] = {};
+    bool bcTimed = false;
 
     // instanced block meshes and their emissive-triangle lights
     struct BlockDef {
@@ -2248,7 +2252,7 @@ void vxpt_destroy(vxpt_ctx *c) {
         if (e) hipEventDestroy(e);
     for (WbRec *p : c->editStage)
         if (p) hipHostFree(p);
-    for (hipEvent_t e : {c->instWritten, c->ibEv[0], c->ibEv[1]})
+    for (hipEvent_t e : {c->instWritten, c->ibEv[0], c->ibEv[1], c->bcEv[0], c->bcEv[1]})
         if (e) hipEventDestroy(e);
     for (auto &s : c->instStage) {
         if (s.done) hipEventDestroy(s.done);
@@ -2741,11 +2745,64 @@ int vxpt_load_textures(vxpt_ctx *c, const char *root, int *loaded) {
     return VXPT_OK;
 }
 
+namespace {
+
+// device buffers of one encode, freed when it ends (a texture load is rare: nothing is kept)
+struct BcEncTemp {
+    uint32_t *src = nullptr;
+    BcEncJob *jobs = nullptr;
+    ~BcEncTemp() {
+        if (src) hipFree(src);
+        if (jobs) hipFree(jobs);
+    }
+};
+
+void push_level_jobs(std::vector<BcEncJob> &jobs, uint32_t src, int w, int h, uint32_t dst, int bpb) {
+    for (int by = 0; by < h / 4; ++by)
+        for (int bx = 0; bx < w / 4; ++bx)
+            jobs.push_back(BcEncJob{src, (uint32_t)w, (uint16_t)bx, (uint16_t)by, dst + (uint32_t)((size_t)by * (w / 4) + bx) * bpb});
+}
+
+// The jobs of each format (BC4, BC5, BC7) encoded into out on the context stream, one launch per
+// format, between the events vxpt_bc_encode_ms reads; nTexels RGBA8 texels are uploaded for them.
+int device_encode(vxpt_ctx *c, const uint8_t *rgba, size_t nTexels, const std::vector<BcEncJob> jobs[3], int quality,
+                  uint8_t *out) {
+    BcEncTemp tmp;
+    const size_t nJobs = jobs[0].size() + jobs[1].size() + jobs[2].size();
+    if (nJobs == 0) return VXPT_OK;
+    for (auto &e : c->bcEv)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    HIPCHK(c, hipMalloc((void **)&tmp.src, nTexels * 4));
+    HIPCHK(c, hipMalloc((void **)&tmp.jobs, nJobs * sizeof(BcEncJob)));
+    HIPCHK(c, hipMemcpyAsync(tmp.src, rgba, nTexels * 4, hipMemcpyHostToDevice, c->stream));
+    size_t at = 0;
+    for (int f = 0; f < 3; ++f) {
+        if (!jobs[f].empty())
+            HIPCHK(c, hipMemcpyAsync(tmp.jobs + at, jobs[f].data(), jobs[f].size() * sizeof(BcEncJob), hipMemcpyHostToDevice, c->stream));
+        at += jobs[f].size();
+    }
+    HIPCHK(c, hipEventRecord(c->bcEv[0], c->stream));
+    const int formats[3] = {bcn::kBc4, bcn::kBc5, bcn::kBc7};
+    at = 0;
+    for (int f = 0; f < 3; ++f) {
+        HIPCHK(c, launch_bc_encode(formats[f], tmp.src, tmp.jobs + at, (int)jobs[f].size(), quality, out, c->stream));
+        at += jobs[f].size();
+    }
+    HIPCHK(c, hipEventRecord(c->bcEv[1], c->stream));
+    c->bcTimed = true;
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the temporaries are freed on return
+    return VXPT_OK;
+}
+
+}  // namespace
+
 // The same set with every level as BC7 / BC5 / BC4 blocks (TextureManager.cu:189-330): the format
 // from the PNG's channel count (:193-210), each level's blocks from its cache file or the encoder
 // (bcn.hpp level_blocks; :271-287), every chain padded to 16 bytes so that BC7 / BC5 levels start
 // aligned (a BC4 level is a multiple of 8).  VXPT_TEX_EXPAND decodes the blocks back into the
 // RGBA8 buffer (same offsets as vxpt_load_textures) and samples that.
+// VXPT_TEX_ENCODE_SEARCH: the levels without a cache file are encoded at quality 1 by the device
+// encoders, straight into the block buffer, and read back only for the cache files and the expansion.
 int vxpt_load_textures_bc(vxpt_ctx *c, const char *root, const char *cache_dir, int flags, int *loaded,
                           int *levels_from_cache) {
     if (!c) return VXPT_ERR_ARG;
@@ -2759,19 +2816,36 @@ int vxpt_load_textures_bc(vxpt_ctx *c, const char *root, const char *cache_dir, 
     std::vector<uint8_t> blocks, level;
     std::vector<TexBcInfo> bcTable;
     int cached = 0;
-    const bool expand = (flags & VXPT_TEX_EXPAND) != 0;
+    const bool expand = (flags & VXPT_TEX_EXPAND) != 0, search = (flags & VXPT_TEX_ENCODE_SEARCH) != 0;
+    const bool writeCache = (flags & VXPT_TEX_WRITE_CACHE) != 0;
+    const std::string cacheDir = cache_dir ? cache_dir : "";
+    std::vector<BcEncJob> jobs[3];  // search: the uncached levels' blocks by format (BC4, BC5, BC7)
+    struct Pending { size_t tex; int lod; };
+    std::vector<Pending> pending;
     for (size_t i = 0; i < table.size(); ++i) {
         TexBcInfo bi{};
         bi.format = bcn::format_of_channels(channels[i]);
         for (int l = 0; l <= table[i].maxLod; ++l) {
             const int S = table[i].size >> l;
             uint8_t *rgba = reinterpret_cast<uint8_t *>(texels.data() + table[i].off[l]);
-            cached += bcn::level_blocks(bi.format, rgba, S, cache_dir ? cache_dir : "", texPaths[i], l,
-                                        (flags & VXPT_TEX_WRITE_CACHE) != 0, level) ? 1 : 0;
+            bool hit;
+            if (search) {
+                hit = bcn::read_cache_level(bi.format, S, cacheDir, texPaths[i], l, level);
+                if (!hit) std::fill(level.begin(), level.end(), (uint8_t)0);
+            } else {
+                hit = bcn::level_blocks(bi.format, rgba, S, cacheDir, texPaths[i], l, writeCache, level);
+            }
+            cached += hit ? 1 : 0;
             if (blocks.size() + level.size() > 0xfffffff0ull) return fail(c, VXPT_ERR_ARG, "texture blocks exceed 4 GiB");
             bi.off[l] = (unsigned)blocks.size();
             blocks.insert(blocks.end(), level.begin(), level.end());
-            if (expand) bcn::decode(bi.format, level.data(), S / 4, S / 4, rgba);
+            if (search && !hit) {
+                push_level_jobs(jobs[bi.format == bcn::kBc4 ? 0 : bi.format == bcn::kBc5 ? 1 : 2], table[i].off[l], S, S,
+                                bi.off[l], bcn::bytes_per_block(bi.format));
+                pending.push_back(Pending{i, l});
+            } else if (expand) {
+                bcn::decode(bi.format, level.data(), S / 4, S / 4, rgba);
+            }
         }
         blocks.resize((blocks.size() + 15) & ~(size_t)15);
         bcTable.push_back(bi);
@@ -2782,10 +2856,28 @@ int vxpt_load_textures_bc(vxpt_ctx *c, const char *root, const char *cache_dir, 
     c->nTexBlockBytes = blocks.size();
     c->texBcOn = !expand && !table.empty();
     if (!table.empty()) {
+        if (!pending.empty()) {
+            // the cached levels' bytes go up with the buffer; the kernels fill in the rest in place
+            if (int r = upload_vec(c, c->texBlocks, blocks.data(), blocks.size())) return r;
+            if (int r = device_encode(c, reinterpret_cast<const uint8_t *>(texels.data()), texels.size(), jobs, 1, c->texBlocks.p))
+                return r;
+            if (expand || (writeCache && !cacheDir.empty())) {
+                HIPCHK(c, hipMemcpy(blocks.data(), c->texBlocks.p, blocks.size(), hipMemcpyDeviceToHost));
+                for (const Pending &pd : pending) {
+                    const int S = table[pd.tex].size >> pd.lod, fmt = bcTable[pd.tex].format;
+                    const uint8_t *lv = blocks.data() + bcTable[pd.tex].off[pd.lod];
+                    if (writeCache)
+                        bcn::write_cache_level(cacheDir, texPaths[pd.tex], pd.lod, lv, (size_t)S * S / 16 * bcn::bytes_per_block(fmt));
+                    if (expand)
+                        bcn::decode(fmt, lv, S / 4, S / 4, reinterpret_cast<uint8_t *>(texels.data() + table[pd.tex].off[pd.lod]));
+                }
+            }
+        } else if (!expand) {
+            if (int r = upload_vec(c, c->texBlocks, blocks.data(), blocks.size())) return r;
+        }
         if (expand) {
             if (int r = upload_vec(c, c->texels, texels.data(), texels.size())) return r;
         } else {
-            if (int r = upload_vec(c, c->texBlocks, blocks.data(), blocks.size())) return r;
             if (int r = upload_vec(c, c->texBcTable, bcTable.data(), bcTable.size())) return r;
         }
         if (int r = upload_vec(c, c->texTable, table.data(), table.size())) return r;
@@ -2794,6 +2886,33 @@ int vxpt_load_textures_bc(vxpt_ctx *c, const char *root, const char *cache_dir, 
     c->texEnabled = table.empty() ? 0 : 1;
     if (loaded) *loaded = (int)table.size();
     if (levels_from_cache) *levels_from_cache = cached;
+    return VXPT_OK;
+}
+
+int vxpt_bc_encode_device(vxpt_ctx *c, int format, const uint8_t *rgba, int w, int h, int quality, void *blocks_out) {
+    if (!c || (format != bcn::kBc4 && format != bcn::kBc5 && format != bcn::kBc7) || !rgba || w <= 0 || h <= 0 || (w & 3) ||
+        (h & 3) || w > 262144 || h > 262144 || (quality != 0 && quality != 1) || !blocks_out)
+        return VXPT_ERR_ARG;
+    const size_t bytes = (size_t)(w / 4) * (h / 4) * bcn::bytes_per_block(format);
+    if ((size_t)w * h > 0x40000000ull) return fail(c, VXPT_ERR_ARG, "image exceeds 2^30 texels");
+    HIPCHK(c, hipSetDevice(c->dev));
+    std::vector<BcEncJob> jobs[3];
+    push_level_jobs(jobs[format == bcn::kBc4 ? 0 : format == bcn::kBc5 ? 1 : 2], 0u, w, h, 0u, bcn::bytes_per_block(format));
+    uint8_t *out = nullptr;
+    HIPCHK(c, hipMalloc((void **)&out, bytes));
+    int r = device_encode(c, rgba, (size_t)w * h, jobs, quality, out);
+    if (r == VXPT_OK && hipMemcpy(blocks_out, out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        r = fail(c, VXPT_ERR_HIP, "reading the encoded blocks back");
+    hipFree(out);
+    return r;
+}
+
+int vxpt_bc_encode_ms(vxpt_ctx *c, float *ms) {
+    if (!c || !ms) return VXPT_ERR_ARG;
+    if (!c->bcTimed) return fail(c, VXPT_ERR_STATE, "no device encode yet");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipEventSynchronize(c->bcEv[1]));
+    HIPCHK(c, hipEventElapsedTime(ms, c->bcEv[0], c->bcEv[1]));
     return VXPT_OK;
 }
 

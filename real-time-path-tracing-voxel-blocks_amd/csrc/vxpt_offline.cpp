@@ -59,6 +59,7 @@ struct Options {
     bool textures = true;
     // block-compressed textures (vxpt_load_textures_bc): blocks decoded in the sampler, or expanded to RGBA8
     bool bcTextures = false, expandTextures = false;
+    int bcEncoder = -1;  // --bc-encoder: 0 fast, 1 search (VXPT_TEX_ENCODE_SEARCH); -1: not given
     std::string textureCache;  // the reference's cache directory (<name>_lod_<n>.bin); empty: none
     // render scale: trace at renderWidth x renderHeight, save width x height (1: no upscale at all)
     float renderScale = 1.0f, sharpness = 1.0f;
@@ -114,6 +115,8 @@ void usage(const char *argv0) {
               << "  --texture-cache <dir>  Read <name>_lod_<n>.bin block files from <dir> (the reference's texture\n"
               << "                         cache) and write the levels encoded here; implies --bc-textures\n"
               << "  --expand-textures      With --bc-textures: decode the blocks to RGBA8 texels on the host\n"
+              << "  --bc-encoder <e>       With --bc-textures: fast (default; the host encoder) or search (the search\n"
+              << "                         encoder on the device) for the levels that have no cache file\n"
               << "  --render-scale <s>     Trace at s times the output size, 0.25 <= s <= 1 (default: 1); each side is\n"
               << "                         rounded to a multiple of 8 (at least 8) and the frame is scaled up to\n"
               << "                         --width x --height before it is saved.  The post-process runs at the\n"
@@ -177,6 +180,17 @@ int parse(int argc, char **argv, Options &o) {
         else if (a == "--bc-textures") o.bcTextures = true;
         else if (a == "--expand-textures") o.bcTextures = o.expandTextures = true;
         else if (a == "--texture-cache") { if ((v = next("--texture-cache"))) { o.textureCache = v; o.bcTextures = true; } }
+        else if (a == "--bc-encoder") {
+            if ((v = next("--bc-encoder"))) {
+                const std::string m = v;
+                if (m == "fast") o.bcEncoder = 0;
+                else if (m == "search") o.bcEncoder = 1;
+                else {
+                    std::cerr << "--bc-encoder takes fast or search\n";
+                    return -1;
+                }
+            }
+        }
         else if (a == "--render-scale") { if ((v = next("--render-scale"))) { o.renderScale = (float)std::atof(v); } }
         else if (a == "--sharpness") { if ((v = next("--sharpness"))) { o.sharpness = (float)std::atof(v); } }
         else if (a == "--upscale") {
@@ -257,6 +271,10 @@ int parse(int argc, char **argv, Options &o) {
     }
     if (!(o.renderScale >= 0.25f && o.renderScale <= 1.0f) || !(o.sharpness >= 0.0f && o.sharpness <= 1.0f)) {
         std::cerr << "render-scale must lie in [0.25, 1] and sharpness in [0, 1]\n";
+        return -1;
+    }
+    if (o.bcEncoder >= 0 && !o.bcTextures) {
+        std::cerr << "--bc-encoder needs --bc-textures\n";
         return -1;
     }
     if (o.skyBuild < 0) o.skyBuild = o.todRange ? 1 : 0;
@@ -414,7 +432,8 @@ int main(int argc, char **argv) {
         int nTex = 0;
         if (o.bcTextures) {
             int nCached = 0;
-            const int flags = (o.textureCache.empty() ? 0 : VXPT_TEX_WRITE_CACHE) | (o.expandTextures ? VXPT_TEX_EXPAND : 0);
+            const int flags = (o.textureCache.empty() ? 0 : VXPT_TEX_WRITE_CACHE) | (o.expandTextures ? VXPT_TEX_EXPAND : 0) |
+                              (o.bcEncoder == 1 ? VXPT_TEX_ENCODE_SEARCH : 0);
             if (vxpt_load_textures_bc(ctx, nullptr, o.textureCache.empty() ? nullptr : o.textureCache.c_str(), flags, &nTex,
                                       &nCached) != VXPT_OK)
                 return fail("loading textures");

@@ -35,7 +35,7 @@ INSTANCE_BUILD = dict(host=0, device=1)
 UPSCALE_BICUBIC, UPSCALE_EASU, UPSCALE_EASU_SHARPEN = 0, 1, 2
 # vxpt_bc_format / vxpt_texture_flags
 BC4, BC5, BC7 = 4, 5, 7
-TEX_WRITE_CACHE, TEX_EXPAND = 1, 2
+TEX_WRITE_CACHE, TEX_EXPAND, TEX_ENCODE_SEARCH = 1, 2, 4
 FLOAT1_BUFS = {1, 5, 12, 13, 19, 20, 49}
 RESERVOIR_DTYPE = np.dtype([("lightData", "<u4"), ("uvData", "<u4"), ("weightSum", "<f4"), ("targetPdf", "<f4"),
                             ("M", "<f4")])
@@ -169,6 +169,9 @@ def load_library(path=LIB_PATH):
         "vxpt_texture_table_bc": (I, [P, P, I, P, P]),
         "vxpt_bc_decode": (I, [I, P, I, I, P]),
         "vxpt_bc_encode": (I, [I, P, I, I, P]),
+        "vxpt_bc_encode_q": (I, [I, P, I, I, I, P]),
+        "vxpt_bc_encode_device": (I, [P, I, P, I, I, I, P]),
+        "vxpt_bc_encode_ms": (I, [P, ctypes.POINTER(F)]),
         "vxpt_bc_cache_path": (I, [ctypes.c_char_p, ctypes.c_char_p, I, P, I]),
         "vxpt_bc_level": (I, [I, P, I, ctypes.c_char_p, ctypes.c_char_p, I, I, P, P]),
         "vxpt_probe_texture": (I, [P, I, I, P, P]),
@@ -375,16 +378,35 @@ class Renderer:
                   "vxpt_load_textures")
         return n.value
 
-    def load_textures_bc(self, root=None, cache_dir=None, write_cache=False, expand=False):
+    def load_textures_bc(self, root=None, cache_dir=None, write_cache=False, expand=False, encoder="fast"):
         """The texture set as BC7 / BC5 / BC4 blocks (TextureManager.cu:189-330), levels taken from
         <cache_dir>/<name>_lod_<l>.bin where present; expand: decoded on the host into the RGBA8
-        buffer.  -> (textures loaded, levels taken from cache files)."""
+        buffer; encoder: "fast" (the host encoder) or "search" (quality 1 on the device) for the
+        levels without a cache file.  -> (textures loaded, levels taken from cache files)."""
+        if encoder not in ("fast", "search"):
+            raise VxptError("load_textures_bc: encoder is 'fast' or 'search'")
         n, nc = ctypes.c_int(0), ctypes.c_int(0)
-        flags = (TEX_WRITE_CACHE if write_cache else 0) | (TEX_EXPAND if expand else 0)
+        flags = ((TEX_WRITE_CACHE if write_cache else 0) | (TEX_EXPAND if expand else 0) |
+                 (TEX_ENCODE_SEARCH if encoder == "search" else 0))
         self._chk(self.lib.vxpt_load_textures_bc(self.ctx, os.fsencode(str(root)) if root else None,
                                                  os.fsencode(str(cache_dir)) if cache_dir else None, flags,
                                                  ctypes.byref(n), ctypes.byref(nc)), "vxpt_load_textures_bc")
         return n.value, nc.value
+
+    def bc_encode(self, fmt, rgba, quality=1):
+        """bc_encode through the device encoders: the same bytes as the host's at that quality."""
+        img = _rgba8(rgba, "bc_encode")
+        h, w = img.shape[:2]
+        out = np.zeros((h // 4) * (w // 4) * bc_bytes_per_block(fmt), np.uint8)
+        self._chk(self.lib.vxpt_bc_encode_device(self.ctx, int(fmt), _ptr(img), w, h, int(quality), _ptr(out)),
+                  "vxpt_bc_encode_device")
+        return out
+
+    def bc_encode_ms(self):
+        """GPU time of the last device encode (bc_encode, or a search load that encoded levels); waits for it."""
+        ms = ctypes.c_float()
+        self._chk(self.lib.vxpt_bc_encode_ms(self.ctx, ctypes.byref(ms)), "vxpt_bc_encode_ms")
+        return ms.value
 
     def texture_table_bc(self):
         """[(format, size, maxLod, [level offsets in bytes into TEX_BLOCKS])], total bytes."""
@@ -1123,16 +1145,25 @@ def bc_decode(fmt, blocks, n_blocks_x, n_blocks_y):
     return out
 
 
-def bc_encode(fmt, rgba):
-    """uint8 [h, w, 4] (multiples of 4) -> uint8 block bytes, deterministic (no GPU needed)."""
-    lib = load_library()
+def _rgba8(rgba, what):
     img = np.ascontiguousarray(rgba, np.uint8)
-    h, w = img.shape[:2]
     if img.ndim != 3 or img.shape[2] != 4:
-        raise VxptError("bc_encode: RGBA8 expected")
+        raise VxptError("%s: RGBA8 expected" % what)
+    return img
+
+
+def bc_encode(fmt, rgba, quality=0):
+    """uint8 [h, w, 4] (multiples of 4) -> uint8 block bytes, deterministic (no GPU needed).
+    quality 0: the fast encoder; 1: the search, in which no block is worse than at 0."""
+    lib = load_library()
+    img = _rgba8(rgba, "bc_encode")
+    h, w = img.shape[:2]
     out = np.zeros((h // 4) * (w // 4) * bc_bytes_per_block(fmt), np.uint8)
-    if lib.vxpt_bc_encode(int(fmt), _ptr(img), w, h, _ptr(out)) != 0:
-        raise VxptError("vxpt_bc_encode failed")
+    if quality == 0:
+        if lib.vxpt_bc_encode(int(fmt), _ptr(img), w, h, _ptr(out)) != 0:
+            raise VxptError("vxpt_bc_encode failed")
+    elif lib.vxpt_bc_encode_q(int(fmt), _ptr(img), w, h, int(quality), _ptr(out)) != 0:
+        raise VxptError("vxpt_bc_encode_q failed")
     return out
 
 
