@@ -33,6 +33,31 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def _nm():
+    import glob
+    import shutil
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    for pat in ("llvm/bin/llvm-nm", "lib/llvm/bin/llvm-nm"):
+        hits = glob.glob(os.path.join(rocm, pat))
+        if hits:
+            return hits[0]
+    return shutil.which("llvm-nm") or shutil.which("nm")
+
+
+def test_host_runtime_internals_are_not_exported():
+    # the host runtime's cross-file functions (csrc/host_ctx.hpp, namespace vx::host) are declared
+    # hidden: none of them is a dynamic symbol of the library
+    import subprocess
+    assert os.path.exists(LIB), "libvxpt.so not built: run __graft_entry__.build()"
+    nm = _nm()
+    assert nm, "neither llvm-nm under the ROCm install nor nm on the path"
+    out = subprocess.run([nm, "-D", "--defined-only", LIB], check=True, capture_output=True, text=True).stdout
+    names = [ln.split()[-1] for ln in out.splitlines() if ln.split()]
+    assert any(n == "vxpt_create" for n in names)  # the listing is the library's
+    leaked = [n for n in names if n.startswith("_ZN2vx4host")]
+    assert not leaked, leaked
+
+
 def test_library_has_gfx950_code_object():
     # the fat binary embeds the offload bundle id of every device code object
     blob = open(LIB, "rb").read()

@@ -3,7 +3,7 @@
 (vxpt_config row_begin / row_end: the trace and denoiser over the band's rows only, no exchange),
 for N = 1 / 2 / 4 / 8 bands -- the equal bands, then the cost-balanced ones bench.py runs (three rounds
 of vxpt_band_balance on these same band times) -- plus the halo bytes the library's band schedule moves per rank and frame
-(band_frame in vxpt_host.cpp) and their time on one xGMI link.
+(band_frame in host_bands.cpp) and their time on one xGMI link.
 
 python tools/band_proxy.py [WIDTH HEIGHT] [--out profiles/r05_band_proxy.json]
 """
@@ -21,7 +21,7 @@ from bench import C1_DIR, band_tuning  # noqa: E402
 
 XGMI_GBS = 153.0   # one xGMI link, one direction (MI355X_MICROARCH.md: 7 links x ~153 GB/s per GPU)
 GROUP_US = 15.0    # latency charged per ordered RCCL group (send/recv to the neighbours), not measurable here
-TRACE_ROWS, HIST_ROWS, PLANE_ROWS = 72, 2, 40   # static camera (vxpt_host.cpp band_frame)
+TRACE_ROWS, HIST_ROWS, PLANE_ROWS = 72, 2, 40   # static camera (host_bands.cpp band_frame)
 PLANE_B = 16 + 16 + 16 + 16 + 4 + 4             # depth, normalRough, geoNormalThin, albedo, material, matParam
 
 
