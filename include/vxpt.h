@@ -247,6 +247,32 @@ int vxpt_generate_terrain(vxpt_ctx *ctx, int chunks_x, int chunks_y, int chunks_
                           float freq_den, int flags);
 /* upload an explicit grid: chunk-major, 32^3 per chunk, x + 32*(z + 32*y) (VoxelChunk.h:12-55) */
 int vxpt_upload_voxels(vxpt_ctx *ctx, const uint8_t *ids, int chunks_x, int chunks_y, int chunks_z);
+/* The same generator with an origin and a seed: another world, or another window of the same one.
+ * The noise sees (float)(origin[0] + x) and (float)(origin[2] + z) for the window's cell (x, ., z), and
+ * the shader balls' row is tested at the same global x / z; origin[1] is added to the compared height,
+ * and only with VXPT_TERRAIN_GLOBAL_Y (without it, it must be 0).  Origin 0 and seed 124 give
+ * vxpt_generate_terrain's world.  VXPT_ERR_ARG: chunk counts not positive, freq_den == 0, a non-zero
+ * origin[1] without the flag, or |origin| or |origin + 32 * chunks| reaching 2^24 on any axis (the
+ * int -> float conversion must stay exact).
+ *   vxpt_generate_terrain_ex: in VXPT_WORLD_BUILD_DEVICE mode the ids are generated on the device (only
+ * the 256-byte permutation table crosses to it), the tables are built there as for an upload, and the
+ * host mirrors are read back from what the device holds instead of rebuilt: one wait for the GPU.  In
+ * VXPT_WORLD_BUILD_HOST mode it is vxpt_terrain_host followed by vxpt_upload_voxels.  Either way the
+ * world afterwards equals vxpt_upload_voxels of vxpt_terrain_host's ids, and histories are as stale as
+ * after any upload.  Banded and linked contexts: call it on every member (each owns its world).
+ *   vxpt_terrain_host: the chunk-major ids alone, 32768 * chunks bytes; no context, no GPU.
+ *   vxpt_terrain_ms: event times of the last device-mode _ex call: height kernel, fill kernel, table
+ * kernels, mirror readback (VXPT_ERR_STATE when the last call did not take the device path). */
+typedef struct {
+    int chunks[3];
+    float height_scale, freq_den;
+    int flags;              /* as vxpt_generate_terrain */
+    int origin[3];          /* cells added to the window's x, y, z before the noise / height compare */
+    unsigned seed;          /* 124 = vxpt_generate_terrain's world */
+} vxpt_terrain_desc;
+int vxpt_generate_terrain_ex(vxpt_ctx *ctx, const vxpt_terrain_desc *desc);
+int vxpt_terrain_host(const vxpt_terrain_desc *desc, uint8_t *ids);
+int vxpt_terrain_ms(vxpt_ctx *ctx, float out[4]);
 /* MaterialManager GPU table (MaterialManager.cpp:60-170) for block ids 1..12 */
 int vxpt_upload_materials(vxpt_ctx *ctx, const vxpt_material *mats, int n_block_ids);
 /* SkyModel::update (Sky.cu:355-396): sky + sun maps on the GPU, alias tables on the host */

@@ -1,4 +1,4 @@
-// vxpt -- the one internal header of the host runtime (vxpt_host.cpp, host_bands.cpp) behind the C ABI (include/vxpt.h):
+// vxpt -- the one internal header of the host runtime (vxpt_host.cpp, host_bands.cpp, host_terrain.cpp) behind the C ABI (include/vxpt.h):
 // the context, its allocation helpers, and the host functions that are called across files.
 //
 // The library is built with default visibility: everything in vx::host is declared hidden here, so
@@ -113,6 +113,14 @@ struct vxpt_ctx {
     int editNext = 0;
     hipEvent_t worldWritten = nullptr, wbEv[2] = {};
     bool wbTimed = false;
+    // terrain generated on the device (vxpt_generate_terrain_ex; terrain.hip): the permutation table, the
+    // window's height plane, the two counts k_terrain_mirrors adds for the host mirrors, and the events
+    // around the last call's height, fill and table kernels and its readback (vxpt_terrain_ms)
+    DBuf<uint8_t> terPerm, dNonAir;
+    DBuf<float> terHeight;
+    DBuf<int> dTopCount;
+    hipEvent_t terEv[5] = {};
+    bool terTimed = false;
     MatDev mats[32] = {};  // by block id: 1..12 cubes (kernel arguments), 13..29 instanced meshes (meshMats)
     CamDev cam{}, prevCam{};
     float camYaw = 0, camPitch = 0;
@@ -401,6 +409,7 @@ inline const vxpt_denoise_params *denoise_or_yaml(const vxpt_ctx *c, const vxpt_
 }
 
 // vxpt_host.cpp
+int world_from_device(vxpt_ctx *c, hipEvent_t tables, hipEvent_t read);
 hipStream_t front_stream(const vxpt_ctx *c, int set);
 int trace_front(vxpt_ctx *c, int32_t it, uint32_t flags, bool accumulate, bool accumFirst, float accumScale,
                 bool overlap, PassPlan &pl, bool planes = true);

@@ -6,6 +6,7 @@
 #include <vector>
 #include "vx_math.hpp"
 #include "alias_build.hpp"
+#include "terrain.hpp"
 
 namespace vx {
 
@@ -335,6 +336,14 @@ hipError_t launch_wb_tables(const WbWorld &w, const WbRanges &rg, hipStream_t st
 hipError_t launch_wb_sky_top(const WbWorld &w, hipStream_t st);
 // rec: device-readable (pinned host) records, c.n[0] + .. + c.n[4] of them
 hipError_t launch_wb_edit(const WbWorld &w, const WbRec *rec, const WbEditCounts &c, hipStream_t st);
+// the terrain generated on the device (terrain.hip; bodies in terrain.hpp).  perm: the 256-byte
+// permutation table; height: one float per column of the window, x + 32 * cx * z
+hipError_t launch_terrain_height(const ter::Window &t, const uint8_t *perm, float *height, hipStream_t st);
+// height -> the chunk-major ids of the window
+hipError_t launch_terrain_fill(const ter::Window &t, const float *height, uint8_t *ids, hipStream_t st);
+// what the host mirrors hold beside the device tables: non-air cells per brick from the brick-major
+// ids, and cube cells per 64^3 block (topCount, which it clears first) from the cell masks
+hipError_t launch_terrain_mirrors(const WbWorld &w, uint8_t *nonAir, int *topCount, hipStream_t st);
 // the instances' TLAS as a linear BVH built on the device (instances.hip; bodies in lbvh.hpp): n mesh
 // instances, the m-th being instance row miRow[m] of meshRow (cell xyz, block id).  Scratch: packed
 // (npad = lbvh_padded(n) sort words), primBox (6 n), exact (6 (2n - 1)), slotInner (n), slotLeaf (n),

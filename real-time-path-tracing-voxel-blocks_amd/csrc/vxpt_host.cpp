@@ -44,53 +44,6 @@ using namespace vx;
 
 namespace {
 
-// Perlin noise (siv::BasicPerlinNoise<float>, voxelengine/ext/PerlinNoise.hpp:229-494, 565-568)
-struct Perlin {
-    uint8_t p[256];
-    explicit Perlin(uint32_t seed) {
-        for (int i = 0; i < 256; ++i) p[i] = (uint8_t)i;
-        std::mt19937 g(seed);
-        for (int i = 1; i < 256; ++i) {
-            const uint64_t r = (uint64_t)g() % (uint64_t)(i + 1);
-            std::swap(p[i], p[r]);
-        }
-    }
-    static float fade(float t) { return t * t * t * (t * (t * 6 - 15) + 10); }
-    static float lerp(float a, float b, float t) { return a + (b - a) * t; }
-    static float grad(uint8_t hash, float x, float y, float z) {
-        const uint8_t h = hash & 15;
-        const float u = h < 8 ? x : y;
-        const float v = h < 4 ? y : (h == 12 || h == 14 ? x : z);
-        return ((h & 1) == 0 ? u : -u) + ((h & 2) == 0 ? v : -v);
-    }
-    float noise(float x, float y, float z) const {
-        const float X = std::floor(x), Y = std::floor(y), Z = std::floor(z);
-        const int ix = (int)X & 255, iy = (int)Y & 255, iz = (int)Z & 255;
-        const float fx = x - X, fy = y - Y, fz = z - Z;
-        const float u = fade(fx), v = fade(fy), w = fade(fz);
-        const uint8_t A = (p[ix] + iy) & 255, B = (p[(ix + 1) & 255] + iy) & 255;
-        const uint8_t AA = (p[A] + iz) & 255, AB = (p[(A + 1) & 255] + iz) & 255;
-        const uint8_t BA = (p[B] + iz) & 255, BB = (p[(B + 1) & 255] + iz) & 255;
-        const float q0 = lerp(grad(p[AA], fx, fy, fz), grad(p[BA], fx - 1, fy, fz), u);
-        const float q1 = lerp(grad(p[AB], fx, fy - 1, fz), grad(p[BB], fx - 1, fy - 1, fz), u);
-        const float q2 = lerp(grad(p[(AA + 1) & 255], fx, fy, fz - 1), grad(p[(BA + 1) & 255], fx - 1, fy, fz - 1), u);
-        const float q3 = lerp(grad(p[(AB + 1) & 255], fx, fy - 1, fz - 1), grad(p[(BB + 1) & 255], fx - 1, fy - 1, fz - 1), u);
-        return lerp(lerp(q0, q1, v), lerp(q2, q3, v), w);
-    }
-    float octave01(float x, float y, int oct) const {
-        float r = 0, a = 1;
-        for (int i = 0; i < oct; ++i) {
-            r += noise(x, y, (float)0.34567) * a;
-            x *= 2;
-            y *= 2;
-            a *= 0.5f;
-        }
-        if (r <= -1.0f) return 0.0f;
-        if (1.0f <= r) return 1.0f;
-        return r * 0.5f + 0.5f;
-    }
-};
-
 // minimal YAML reader for the reference's settings / scene / asset files:
 // `section:` headers, `key: value` pairs, `- {k: v, ...}` / `properties: {...}` flow maps
 std::string trim(const std::string &s) {
@@ -614,8 +567,8 @@ int wb_publish(vxpt_ctx *c) {
     return 0;
 }
 
-// every table of the uploaded ids (c->voxels) by the kernels; the host mirrors are built already
-int device_build(vxpt_ctx *c) {
+// every table of the ids on the device (c->voxels) by the kernels, enqueued on the context stream
+int device_build_enqueue(vxpt_ctx *c) {
     const int BX = c->cx * 8, BY = c->cy * 8, BZ = c->cz * 8;
     const size_t nB = (size_t)BX * BY * BZ;
     if (nB > (size_t)INT_MAX) return fail(c, VXPT_ERR_ARG, "world too large");
@@ -636,8 +589,49 @@ int device_build(vxpt_ctx *c) {
     HIPCHK(c, launch_wb_prefix(w, c->stream));
     HIPCHK(c, launch_wb_tables(w, wb_whole(c), c->stream));
     HIPCHK(c, launch_wb_sky_top(w, c->stream));
-    if (int r = wb_publish(c)) return r;
+    return wb_publish(c);
+}
+// the same for uploaded ids, waited for; the host mirrors are built already
+int device_build(vxpt_ctx *c) {
+    if (int r = device_build_enqueue(c)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// A world whose ids were written on the device (c->voxels, c->cx / cy / cz set): the tables as
+// device_build_enqueue, then the host mirrors build_mirrors would give for the same ids, read back
+// instead of rebuilt.  The device holds the ids in both layouts, the cell and macro masks and the column
+// tops already; k_terrain_mirrors adds the two counts.  One wait, behind the copies; `tables` and `read`
+// are recorded behind the kernels and behind the copies.
+int device_build_readback(vxpt_ctx *c, hipEvent_t tables, hipEvent_t read) {
+    if (int r = device_build_enqueue(c)) return r;
+    const int wx = c->cx * 32, wy = c->cy * 32, wz = c->cz * 32;
+    const size_t nB = (size_t)c->nBricks, nCol = (size_t)(wx >> 2) * (wz >> 2);
+    const int tx = (wx + 63) / 64, ty = (wy + 63) / 64, tz = (wz + 63) / 64;
+    const size_t nTop = (size_t)tx * ty * tz;
+    if (grow(c, c->dNonAir, nB) || grow(c, c->dTopCount, nTop)) return VXPT_ERR_HIP;
+    hipStream_t st = c->stream;
+    HIPCHK(c, launch_terrain_mirrors(wb_world(c), c->dNonAir.p, c->dTopCount.p, st));
+    HIPCHK(c, hipEventRecord(tables, st));
+    c->hIds.resize(nB * 64);
+    c->hBricks.resize(nB * 64);
+    c->hCell.resize(nB);
+    c->hMacro.resize(nB / 64);
+    c->hNonAir.resize(nB);
+    c->topCount.resize(nTop);
+    std::vector<uint32_t> col(nCol);
+    HIPCHK(c, hipMemcpyAsync(c->hIds.data(), c->voxels.p, nB * 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->hBricks.data(), c->bricks.p, nB * 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->hCell.data(), c->cellMask.p, nB * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->hMacro.data(), c->macro.p, nB / 64 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->hNonAir.data(), c->dNonAir.p, nB, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->topCount.data(), c->dTopCount.p, nTop * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(col.data(), c->dColTop.p, nCol * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipEventRecord(read, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->colTop.assign(col.begin(), col.end());
+    c->topValid = (nTop <= 64) ? 1 : 0;
+    refresh_top(c);
     return 0;
 }
 
@@ -799,6 +793,8 @@ hipError_t firefly_band(const DenoiseArgs &a, bool detect, bool apply, hipStream
 }  // namespace
 
 namespace vx::host {
+
+int world_from_device(vxpt_ctx *c, hipEvent_t tables, hipEvent_t read) { return device_build_readback(c, tables, read); }
 
 MeshDev mesh_dev(const vxpt_ctx *c) {
     return MeshDev{c->tlas.p, c->meshInst.p, c->blas.p, c->blasTri.p, c->blasTriId.p, c->blasRoot.p, c->nMeshInst};
@@ -1331,6 +1327,8 @@ void vxpt_destroy(vxpt_ctx *c) {
         if (e) hipEventDestroy(e);
     for (WbRec *p : c->editStage)
         if (p) hipHostFree(p);
+    for (hipEvent_t e : c->terEv)
+        if (e) hipEventDestroy(e);
     for (hipEvent_t e : {c->instWritten, c->ibEv[0], c->ibEv[1], c->bcEv[0], c->bcEv[1]})
         if (e) hipEventDestroy(e);
     for (auto &s : c->instStage) {
@@ -1495,38 +1493,9 @@ int vxpt_generate_terrain(vxpt_ctx *c, int cxn, int cyn, int czn, float heightSc
     if (!c || cxn <= 0 || cyn <= 0 || czn <= 0) return VXPT_ERR_ARG;
     const bool keepBalls = (flags & VXPT_TERRAIN_SHADER_BALLS) != 0, globalY = (flags & VXPT_TERRAIN_GLOBAL_Y) != 0;
     std::vector<uint8_t> ids((size_t)cxn * cyn * czn * 32768, 0);
-    const Perlin noise(124);
-    const float freq = 1.0f / freqDen, width = heightScale;
-    for (int ch = 0; ch < cxn * cyn * czn; ++ch) {
-        const int gox = (ch % cxn) * 32, goz = ((ch / cxn) % czn) * 32, goy = globalY ? (ch / (cxn * czn)) * 32 : 0;
-        float hmap[32][32];
-        for (int z = 0; z < 32; ++z)
-            for (int x = 0; x < 32; ++x) {
-                const float n = noise.octave01((float)(gox + x) * freq, (float)(goz + z) * freq, 4);
-                float h = std::fmaf(n, 1.4f, -0.7f);  // nvcc --fmad=true contraction of n*1.4f-0.7f
-                h = std::fmax(0.1f, (h + 0.25f) * width);
-                hmap[z][x] = std::fmin(h, width * 0.9f);
-            }
-        for (int y = 0; y < 32; ++y)
-            for (int z = 0; z < 32; ++z)
-                for (int x = 0; x < 32; ++x) {
-                    const float h = hmap[z][x];
-                    uint8_t id = 0;
-                    const float yy = (float)(goy + y);
-                    if (yy < h) {
-                        const float d = h - yy;
-                        if (h < width * (0.25f + 0.05f)) id = d < 3.5f ? 1 : 7;
-                        else if (h < width * (0.25f + 0.6f) && h > width * (0.25f + 0.3f)) id = d < 5.5f ? 3 : 7;
-                        else id = d < 1.5f ? 2 : (d < 5.5f ? 3 : 7);
-                    }
-                    const int gx = gox + x, gz = goz + z;
-                    if (keepBalls && y == 7 && gz == 43 && gx >= 30 && gx <= 39) {
-                        static const uint8_t ball[10] = {17, 21, 22, 23, 24, 25, 26, 27, 28, 29};
-                        id = ball[gx - 30];
-                    }
-                    ids[(size_t)ch * 32768 + x + 32 * (z + 32 * y)] = id;
-                }
-    }
+    uint8_t perm[256];
+    ter::permutation(124, perm);  // PerlinNoiseGenerator(4, 124), VoxelSceneGen.cu:361
+    ter::generate_host(ter::Window{cxn, cyn, czn, 0, 0, 0, 1.0f / freqDen, heightScale, keepBalls, globalY}, perm, ids.data());
     return vxpt_upload_voxels(c, ids.data(), cxn, cyn, czn);
 }
 

@@ -75,6 +75,10 @@ struct Options {
     // --load-world: the world (and, unless --scene is given, the camera) from a saved scene instead of the terrain
     std::string worldYaml, worldChunks;
     bool sceneGiven = false;
+    // --terrain-origin / --terrain-seed: the terrain through vxpt_generate_terrain_ex
+    bool terrainEx = false;
+    int terrainOrigin[3] = {0, 0, 0};
+    unsigned terrainSeed = 124;
 };
 
 const char *upscale_name(int mode) {
@@ -102,6 +106,9 @@ void usage(const char *argv0) {
               << "  --load-world <yaml> <dir>  The world from a saved scene (vxpt_save_world: scene yaml and chunk\n"
               << "                         directory) instead of the generated terrain; its camera too unless\n"
               << "                         --scene is given\n"
+              << "  --terrain-origin <x,y,z>  Cells added to the terrain window's x, y, z (default: 0,0,0; y must be 0)\n"
+              << "  --terrain-seed <n>     Seed of the terrain's noise (default: 124).  With either flag the terrain is\n"
+              << "                         generated on the device when --world-build is device\n"
               << "  --frames <int>         Number of frames to render (default: 64, use 1 for single frame)\n"
               << "  --spp <int>            Samples per pixel per frame (default: 1)\n"
               << "  --chunks <x> <y> <z>   World size in 32^3 chunks (default: 2 1 2)\n"
@@ -254,6 +261,25 @@ int parse(int argc, char **argv, Options &o) {
             o.worldYaml = v;
             if (!(v = next("--load-world"))) return -1;
             o.worldChunks = v;
+        }
+        else if (a == "--terrain-origin") {
+            if (!(v = next("--terrain-origin"))) return -1;
+            char tail = 0;
+            if (std::sscanf(v, "%d,%d,%d%c", &o.terrainOrigin[0], &o.terrainOrigin[1], &o.terrainOrigin[2], &tail) != 3) {
+                std::cerr << "--terrain-origin takes X,Y,Z\n";
+                return -1;
+            }
+            o.terrainEx = true;
+        }
+        else if (a == "--terrain-seed") {
+            if (!(v = next("--terrain-seed"))) return -1;
+            char *end = nullptr;
+            o.terrainSeed = (unsigned)std::strtoul(v, &end, 10);
+            if (end == v || *end) {
+                std::cerr << "--terrain-seed takes an unsigned integer\n";
+                return -1;
+            }
+            o.terrainEx = true;
         }
         else if (a == "--test-sequence") o.testSequence = true;
         else if (a == "--test-remove20") o.removal20 = true;
@@ -450,6 +476,10 @@ int main(int argc, char **argv) {
         if (vxpt_load_world(ctx, o.worldYaml.c_str(), o.worldChunks.c_str(), &worldCam) != VXPT_OK)
             return fail("loading the world");
         std::cout << "World loaded: " << o.worldYaml << std::endl;
+    } else if (o.terrainEx) {
+        const vxpt_terrain_desc td{{o.chunks[0], o.chunks[1], o.chunks[2]}, 32.0f, 32.0f * o.chunks[0], 0,
+                                   {o.terrainOrigin[0], o.terrainOrigin[1], o.terrainOrigin[2]}, o.terrainSeed};
+        if (vxpt_generate_terrain_ex(ctx, &td) != VXPT_OK) return fail("generating terrain");
     } else if (vxpt_generate_terrain(ctx, o.chunks[0], o.chunks[1], o.chunks[2], 32.0f, 32.0f * o.chunks[0], 0) != VXPT_OK)
         return fail("generating terrain");
     // VoxelEngine::init (VoxelEngine.cu:809-816): the instanced meshes, their instances in the world and

@@ -125,6 +125,18 @@ class Timing(ctypes.Structure):
                 ("frame_ms", ctypes.c_float), ("host_ms", ctypes.c_float)]
 
 
+class TerrainDesc(ctypes.Structure):  # vxpt_terrain_desc
+    _fields_ = [("chunks", ctypes.c_int * 3), ("height_scale", ctypes.c_float), ("freq_den", ctypes.c_float),
+                ("flags", ctypes.c_int), ("origin", ctypes.c_int * 3), ("seed", ctypes.c_uint)]
+
+
+def _terrain_desc(chunks, height_scale, freq_den, flags, origin, seed):
+    if freq_den is None:
+        freq_den = 32.0 * chunks[0]
+    return TerrainDesc((ctypes.c_int * 3)(*[int(v) for v in chunks]), float(height_scale), float(freq_den), int(flags),
+                       (ctypes.c_int * 3)(*[int(v) for v in origin]), int(seed) & 0xFFFFFFFF)
+
+
 class BandStat(ctypes.Structure):  # vxpt_band_stat
     _fields_ = [("frames", ctypes.c_int32), ("groups", ctypes.c_int32), ("groups_ordered", ctypes.c_int32),
                 ("exchange_ms", ctypes.c_float), ("exchange_overlap_ms", ctypes.c_float),
@@ -153,6 +165,9 @@ def load_library(path=LIB_PATH):
         "vxpt_load_scene_camera": (I, [P, ctypes.c_char_p, ctypes.POINTER(Camera)]),
         "vxpt_generate_terrain": (I, [P, I, I, I, F, F, I]),
         "vxpt_upload_voxels": (I, [P, P, I, I, I]),
+        "vxpt_generate_terrain_ex": (I, [P, ctypes.POINTER(TerrainDesc)]),
+        "vxpt_terrain_host": (I, [ctypes.POINTER(TerrainDesc), P]),
+        "vxpt_terrain_ms": (I, [P, P]),
         "vxpt_upload_materials": (I, [P, ctypes.POINTER(Material), I]),
         "vxpt_set_sky": (I, [P, F, F, F, F]),
         "vxpt_set_sky_device": (I, [P, F, F, F, F]),
@@ -323,13 +338,26 @@ class Renderer:
         return cam
 
     def generate_terrain(self, chunks=(2, 1, 2), height_scale=32.0, freq_den=None, keep_shader_balls=False,
-                         global_y=False):
+                         global_y=False, origin=(0, 0, 0), seed=124, ex=False):
+        """vxpt_generate_terrain; with another origin or seed, or ex=True, vxpt_generate_terrain_ex (in
+        device world-build mode the terrain is then generated on the device)."""
         if freq_den is None:
             freq_den = 32.0 * chunks[0]
         flags = (1 if keep_shader_balls else 0) | (2 if global_y else 0)
-        self._chk(self.lib.vxpt_generate_terrain(self.ctx, chunks[0], chunks[1], chunks[2], float(height_scale),
-                                                 float(freq_den), flags), "vxpt_generate_terrain")
+        if ex or tuple(origin) != (0, 0, 0) or seed != 124:
+            d = _terrain_desc(chunks, height_scale, freq_den, flags, origin, seed)
+            self._chk(self.lib.vxpt_generate_terrain_ex(self.ctx, ctypes.byref(d)), "vxpt_generate_terrain_ex")
+        else:
+            self._chk(self.lib.vxpt_generate_terrain(self.ctx, chunks[0], chunks[1], chunks[2], float(height_scale),
+                                                     float(freq_den), flags), "vxpt_generate_terrain")
         self.chunks = tuple(chunks)
+
+    def terrain_ms(self):
+        """vxpt_terrain_ms: milliseconds of the last device-mode generate_terrain(ex): height kernel, fill
+        kernel, table kernels, mirror readback."""
+        out = np.zeros(4, np.float32)
+        self._chk(self.lib.vxpt_terrain_ms(self.ctx, _ptr(out)), "vxpt_terrain_ms")
+        return out
 
     def upload_voxels(self, ids, chunks):
         ids = np.ascontiguousarray(ids, dtype=np.uint8)
@@ -902,6 +930,21 @@ def lbvh_host(boxes, keys):
     if rc != 0:
         raise VxptError("vxpt_lbvh_host failed (%d)" % rc)
     return nodes, order
+
+
+def terrain_host(chunks=(2, 1, 2), height_scale=32.0, freq_den=None, flags=0, origin=(0, 0, 0), seed=124):
+    """vxpt_terrain_host: the generator's chunk-major ids (32768 per chunk) for a window at `origin` of the
+    world of `seed`; no context, no GPU.  flags: 1 shader balls, 2 global y."""
+    lib = load_library()
+    d = _terrain_desc(chunks, height_scale, freq_den, flags, origin, seed)
+    n = max(int(chunks[0]), 0) * max(int(chunks[1]), 0) * max(int(chunks[2]), 0) * 32768
+    if n > (1 << 32):
+        raise VxptError("terrain_host: %d cells do not fit a host array" % n)
+    ids = np.zeros(n, np.uint8)
+    rc = lib.vxpt_terrain_host(ctypes.byref(d), _ptr(ids))
+    if rc != 0:
+        raise VxptError("vxpt_terrain_host failed (%d)" % rc)
+    return ids
 
 
 def world_tables_host(ids, chunks, box_cap=32, box_cap_up=32):
