@@ -5,7 +5,7 @@ denoises only those rows into full-frame buffers.  Every pass that reads a
 neighbourhood is preceded by an exchange of the rows it reads outside the
 band, taken from the ranks that own them -- so the banded render is the
 single-GPU render, bit for bit.  The schedule below mirrors one
-OfflineBackend::renderFrame (vxpt_render_frame / do_denoise in vxpt_host.cpp)
+OfflineBackend::renderFrame (vxpt_render_frame / do_denoise in host_frame.cpp)
 with the exchanges inserted:
 
   trace pass s      -> G-buffer + reservoirs of that pass, TRACE_HALO rows:

@@ -1,7 +1,7 @@
 // vxpt -- a parallel alias-table construction, its bodies shared by the host twin
 // (vxpt_alias_build_host) and the kernels in sky.hip (vxpt_alias_build, vxpt_set_sky_device).
 //
-// The table's inputs are Vose's (build_alias, vxpt_host.cpp): sum = (float) of a double sum of the
+// The table's inputs are Vose's (build_alias, host_sky.cpp): sum = (float) of a double sum of the
 // weights, p[i] = w[i] / sum and s[i] = p[i] * n in binary32.  The double sum is taken in ONE fixed
 // tree order (tree_sum below), the same on the host and on the device:
 //   - the weights are cut into chunks of kChunk = 1024 consecutive items (the last one padded with

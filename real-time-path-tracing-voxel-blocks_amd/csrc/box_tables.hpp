@@ -1,5 +1,5 @@
 // vxpt -- the optional empty-box skip tables of the voxel DDA (host only, no HIP).  Shared by
-// vxpt_host.cpp and the CPU test driver (tests/native/box_tables_driver.cpp).
+// host_world.cpp and the CPU test driver (tests/native/box_tables_driver.cpp).
 //
 // For every empty brick and octant the walk may jump over an empty box of bricks that starts at
 // the brick and extends in the octant's directions.  The default tables hold the largest such

@@ -1,4 +1,4 @@
-// vxpt -- the instanced meshes' BVH builder (host only, no HIP kernels).  Shared by vxpt_host.cpp and
+// vxpt -- the instanced meshes' BVH builder (host only, no HIP kernels).  Shared by host_instances.cpp and
 // the CPU test driver (tests/native/mesh_walk_driver.hip).
 #pragma once
 #include <algorithm>

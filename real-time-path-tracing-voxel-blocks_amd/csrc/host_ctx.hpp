@@ -1,4 +1,5 @@
-// vxpt -- the one internal header of the host runtime (vxpt_host.cpp, host_bands.cpp, host_terrain.cpp) behind the C ABI (include/vxpt.h):
+// vxpt -- the one internal header of the host runtime (vxpt_host.cpp, host_settings.cpp, host_world.cpp, host_sky.cpp,
+// host_textures.cpp, host_instances.cpp, host_frame.cpp, host_bands.cpp, host_terrain.cpp) behind the C ABI (include/vxpt.h):
 // the context, its allocation helpers, and the host functions that are called across files.
 //
 // The library is built with default visibility: everything in vx::host is declared hidden here, so
@@ -50,7 +51,7 @@ constexpr int kMaxSets = 3;      // wavefront state sets (vxpt_ctx::nSets; 4 mea
 
 using namespace vx::host;
 
-vxpt_tuning tuning_defaults();  // vxpt_host.cpp; exported by name like the functions at the end
+vxpt_tuning tuning_defaults();  // host_settings.cpp; exported by name like the functions at the end
 
 struct vxpt_ctx {
     int W = 0, H = 0, dev = 0, rowBegin = 0, rowEnd = 0;
@@ -400,7 +401,7 @@ struct PassPlan {
     int next = 0, set = 0;
 };
 
-constexpr int kWposHalo = 40;  // firefly_band's rows either side of the band (vxpt_host.cpp)
+constexpr int kWposHalo = 40;  // firefly_band's rows either side of the band (host_frame.cpp)
 constexpr int kDenoiseRows = kWposHalo;  // the deepest read of the current G-buffer planes by the denoiser
 
 // the context's denoiser settings for a call that passes none
@@ -409,7 +410,33 @@ inline const vxpt_denoise_params *denoise_or_yaml(const vxpt_ctx *c, const vxpt_
 }
 
 // vxpt_host.cpp
+CamDev make_camera(int W, int H, const vxpt_camera &in, float *yawOut, float *pitchOut);
+bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, void **mirror);
+
+// host_settings.cpp
+std::string trim(const std::string &s);
+std::map<std::string, std::string> parse_flow_map(const std::string &s);
+std::vector<float> parse_list(const std::string &s);
+bool as_bool(const std::string &s);
+vxpt_post_params default_post();
+const vxpt_denoise_params &default_denoise();
+
+// host_world.cpp
+void box_fill(vxpt_ctx *c, int oct, int x0, int x1, int y0, int y1, int z0, int z1);
+void brick_prefix(vxpt_ctx *c);
+int device_tables(vxpt_ctx *c);
 int world_from_device(vxpt_ctx *c, hipEvent_t tables, hipEvent_t read);
+float nearest_surface(const vxpt_ctx *c, V3 p);
+
+// host_sky.cpp
+std::vector<AliasBin> build_alias(const std::vector<float> &w, float &sumOut);
+
+// host_instances.cpp
+MeshDev mesh_dev(const vxpt_ctx *c);
+int edit_instances(vxpt_ctx *c, int x, int y, int z, int old, int block_id);
+
+// host_frame.cpp
+void fill_world(vxpt_ctx *c, WorldDev &w);
 hipStream_t front_stream(const vxpt_ctx *c, int set);
 int trace_front(vxpt_ctx *c, int32_t it, uint32_t flags, bool accumulate, bool accumFirst, float accumScale,
                 bool overlap, PassPlan &pl, bool planes = true);
@@ -422,10 +449,6 @@ int refuse_prefilter(vxpt_ctx *c, const char *sw);
 bool is_banded(const vxpt_ctx *c);
 int do_denoise(vxpt_ctx *c, const vxpt_denoise_params *p, int frameNum, int it);
 int run_pass(vxpt_ctx *c, const vxpt_denoise_params *p, int pass, int arg, int arg2, int margin = 0);
-CamDev make_camera(int W, int H, const vxpt_camera &in, float *yawOut, float *pitchOut);
-bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, void **mirror);
-float nearest_surface(const vxpt_ctx *c, V3 p);
-MeshDev mesh_dev(const vxpt_ctx *c);
 
 // host_bands.cpp
 void gbuf_written(vxpt_ctx *c, int which);
@@ -442,6 +465,9 @@ int band_frame(std::vector<vxpt_ctx *> &cs, const vxpt_denoise_params *p, int fr
 extern "C" {
 int refresh_instances(vxpt_ctx *c, bool lights, bool full);  // instanced meshes (+ lights), after the grid changed
 int refresh_instances_edit(vxpt_ctx *c, bool lights, bool full, const int *edit);  // the same after one edit
+int inst_flush(vxpt_ctx *c);     // what a batch of edits left to enqueue (device instance mode)
+int alias_scratch(vxpt_ctx *c, int n);  // the alias kernels' scratch: the sky's and the light tables' builds share it
+int sky_resolve(vxpt_ctx *c);    // the sun table's sum and the build time of a device sky build
 int post_alloc(vxpt_ctx *c);
 int post_args(vxpt_ctx *c, const vxpt_post_params *pp, float dtMs, PostArgs &a);
 int band_post(std::vector<vxpt_ctx *> &cs, const vxpt_post_params *pp, float dtMs);

@@ -1,6 +1,6 @@
 // vxpt -- host runtime, the terrain with an origin and a seed: the argument checks, the host
 // generator behind vxpt_terrain_host, and the device path of vxpt_generate_terrain_ex (terrain.hip's
-// kernels, then the world's tables and host mirrors from what the device holds: vxpt_host.cpp).
+// kernels, then the world's tables and host mirrors from what the device holds: host_world.cpp).
 #include <cmath>
 #include <cstdint>
 #include <vector>

@@ -1,6 +1,6 @@
 // vxpt -- the light-id remap of a light update (host only, no HIP): VoxelEngine::updateLight's
 // buildLightIdMapping (VoxelEngine.cu:503-539) and buildIncrementalLightMapping (:541-633).
-// Shared by vxpt_host.cpp and the CPU test driver (tests/native/light_map_driver.cpp).
+// Shared by host_instances.cpp and the CPU test driver (tests/native/light_map_driver.cpp).
 #pragma once
 #include <cstdint>
 #include <map>

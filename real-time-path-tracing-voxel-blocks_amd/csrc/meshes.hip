@@ -3,7 +3,7 @@
 // The reference puts every instanced block's mesh into an OptiX IAS (one instance per cell,
 // transform = translation by the cell, VoxelEngine.cu:323-384; OptixRenderer.cpp:723-770) and
 // lets the RT cores find the closest triangle.  Here: a two-level BVH built on the host
-// (vxpt_host.cpp build_mesh_bvh) and walked by one thread per ray -- TLAS over the instances'
+// (host_instances.cpp build_blas / build_tlas) and walked by one thread per ray -- TLAS over the instances'
 // world boxes, then the instance's BLAS in object space with the ray origin translated by
 // -cell (as the IAS transform does) -- with an explicit triangle test:
 //   Moller-Trumbore, plain IEEE products and sums in a fixed order (the oracle repeats it

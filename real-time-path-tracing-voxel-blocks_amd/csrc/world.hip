@@ -1,5 +1,5 @@
 // vxpt -- the world's DDA tables built and edited on gfx950 (vxpt_set_world_build).
-// The host builds the same tables in vxpt_host.cpp (build_occupancy, octant_fill, box_fill,
+// The host builds the same tables in host_world.cpp (build_occupancy, octant_fill, box_fill,
 // upload_sky_top); these kernels produce them bit for bit from the chunk-major ids alone.  Integer
 // work throughout: the order of the atomics and of the lanes cannot change a result.
 #include "vx_internal.hpp"

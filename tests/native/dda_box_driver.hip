@@ -62,7 +62,7 @@ int main(int argc, char **argv) {
     if (!f || fread(ids.data(), 1, ids.size(), f) != ids.size()) return 1;
     fclose(f);
     const size_t nB = (size_t)BX * BY * BZ;
-    auto blin = [&](int bx, int by, int bz) {  // vxpt_host.cpp brick_lin / vx_device.hpp brick_index
+    auto blin = [&](int bx, int by, int bz) {  // host_world.cpp brick_lin / vx_device.hpp brick_index
         const size_t m = (size_t)(bx >> 2) + (size_t)(CX * 2) * ((bz >> 2) + (size_t)(CZ * 2) * (by >> 2));
         return m * 64 + (size_t)((bx & 3) + 4 * ((bz & 3) + 4 * (by & 3)));
     };
@@ -87,7 +87,7 @@ int main(int argc, char **argv) {
                     if (ct < y + 1) ct = (uint16_t)(y + 1);
                 }
             }
-    // the default cube tables (vxpt_host.cpp octant_fill's recurrence, whole grid)
+    // the default cube tables (host_world.cpp octant_fill's recurrence, whole grid)
     std::vector<uint8_t> od(8 * nB, 0);
     for (int oct = 0; oct < 8; ++oct) {
         uint8_t *S = od.data() + oct * nB;

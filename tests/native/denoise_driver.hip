@@ -58,7 +58,7 @@ int main(int argc, char **argv) {
     a.ping = ping.data(); a.pong = pong.data(); a.prevIllum = prevIllum.data(); a.prevFast = prevFast.data();
     a.histLen = histLen.data(); a.prevHistLen = prevHistLen.data();
     a.wpos = wpos.data();
-    // fill_denoise's launch-uniform terms (vxpt_host.cpp)
+    // fill_denoise's launch-uniform terms (host_frame.cpp)
     a.invW = 1.0f / (float)W; a.invH = 1.0f / (float)H;
     a.thrB = a.p.disocclusionThreshold + (1.5f / (float)H);
     a.thrA = a.p.disocclusionThresholdAlternate + (1.5f / (float)H);

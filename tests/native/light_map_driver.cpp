@@ -1,4 +1,4 @@
-// CPU test driver of the library's light-id remap (csrc/light_map.hpp, the code vxpt_host.cpp runs):
+// CPU test driver of the library's light-id remap (csrc/light_map.hpp, the code host_instances.cpp runs):
 // reads a script from stdin and prints each update's remap table.
 //   edit <instance id> <removed 0/1>
 //   update <full 0/1> <prevN> <total> <m> (<id> <first> <count>) x m   -> prints "remap v0 v1 ..."

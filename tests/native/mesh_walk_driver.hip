@@ -1,5 +1,5 @@
 // CPU test driver (host code only, no kernel launch): the library's instanced-mesh BVH (bvh_build.hpp,
-// laid out as vxpt_host.cpp build_blas / build_tlas do) walked by the library's own walk (vx_mesh.hpp,
+// laid out as host_instances.cpp build_blas / build_tlas do) walked by the library's own walk (vx_mesh.hpp,
 // host + device) for the probe kernels' queries (meshes.hip k_mesh_probe / k_mesh_occluded).
 // Usage: mesh_walk_driver meshes.bin rays.bin out.bin
 //   meshes.bin: 32 x (int32 n, n x 9 f32 triangles) per block id, int32 rows, rows x 5 int32

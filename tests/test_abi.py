@@ -44,14 +44,16 @@ def _nm():
     return shutil.which("llvm-nm") or shutil.which("nm")
 
 
-def test_host_runtime_internals_are_not_exported():
+@pytest.mark.parametrize("name", ["libvxpt.so", "libvxpt_stats.so", "libvxpt_exact.so"])
+def test_host_runtime_internals_are_not_exported(name):
     # the host runtime's cross-file functions (csrc/host_ctx.hpp, namespace vx::host) are declared
-    # hidden: none of them is a dynamic symbol of the library
+    # hidden: none of them is a dynamic symbol of the library, nor of the two instrumented builds
     import subprocess
-    assert os.path.exists(LIB), "libvxpt.so not built: run __graft_entry__.build()"
+    lib = os.path.join(os.path.dirname(LIB), name)
+    assert os.path.exists(lib), name + " not built: run __graft_entry__.build()"
     nm = _nm()
     assert nm, "neither llvm-nm under the ROCm install nor nm on the path"
-    out = subprocess.run([nm, "-D", "--defined-only", LIB], check=True, capture_output=True, text=True).stdout
+    out = subprocess.run([nm, "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
     names = [ln.split()[-1] for ln in out.splitlines() if ln.split()]
     assert any(n == "vxpt_create" for n in names)  # the listing is the library's
     leaked = [n for n in names if n.startswith("_ZN2vx4host")]

@@ -83,7 +83,7 @@ int main(int argc, char **argv) {
                 bricks[b * 64 + lc] = id;
                 if (id >= 1 && id <= 12) cellMask[b] |= 1ull << lc;
             }
-    std::vector<uint8_t> od(8 * nB, 0);  // the cube tables (vxpt_host.cpp octant_fill's recurrence)
+    std::vector<uint8_t> od(8 * nB, 0);  // the cube tables (host_world.cpp octant_fill's recurrence)
     for (int oct = 0; oct < 8; ++oct) {
         uint8_t *S = od.data() + oct * nB;
         const int sx = (oct & 1) ? 1 : -1, sy = (oct & 2) ? 1 : -1, sz = (oct & 4) ? 1 : -1;
