@@ -576,6 +576,61 @@ int vxpt_upscale_host(const float *rgba_in, int w, int h, float *rgba_out, int o
                       float sharpness);
 /* size of the last vxpt_upscale and its HIP-event time (waits for it); any pointer may be NULL */
 int vxpt_upscale_info(vxpt_ctx *ctx, int *out_w, int *out_h, float *ms);
+/* Dynamic resolution (the other half of Backend::dynamicResolution, Backend.cpp:191-232): the render size
+ * changed between frames, with the histories carried over.  The size given to vxpt_create becomes the
+ * maximum, which every allocation keeps; 1 <= w <= max_w and 1 <= h <= max_h, anything else is
+ * VXPT_ERR_ARG with nothing changed.  The current size returns VXPT_OK and enqueues nothing.  A context
+ * with a row range, a band communicator or linked contexts is refused (VXPT_ERR_STATE, nothing enqueued).
+ *   Where the reference keeps its surfaces at the maximum size and reprojects across resolutions in uv, this
+ * call resamples every per-pixel buffer that a later frame reads before it writes it -- the denoiser's
+ * histories and history lengths, both reservoir parities, the live slots of the G-buffer ring with their
+ * tap records, an uploaded motion plane -- to the new size, once: new pixel (x, y) takes old pixel
+ * (min(((2x + 1) * old_w) / (2 * w), old_w - 1), the same in y), whole and unblended, so that a pixel's
+ * history stays one old pixel's consistent record.  Buffers that every frame writes before
+ * it reads them (ILLUM, PING, PONG, WPOS, OUTPUT, FRAME, BLOOM) are only re-addressed: they hold
+ * nothing meaningful until the next frame.  The exposure state carries over.  Both cameras take the new
+ * resolution; the previous one keeps its view for the next frame, so that the reprojection lands in the
+ * resampled history (after a resize that changes the aspect ratio it keeps the old size's field of view
+ * until that frame's denoiser -- vxpt_denoise, a frame call, or pass 14 of vxpt_denoise_pass -- has been
+ * enqueued; a caller that only traces sets the cameras again itself; vxpt_render_frames runs that one frame
+ * unpipelined and reports the means over all its frames).  vxpt_readback, vxpt_upload, vxpt_row_bytes and vxpt_upscale's lower bound follow
+ * the new size.
+ *   The call WAITS for everything in flight on the context's streams (a resize is rare), then enqueues
+ * four resample launches on the context stream and returns without waiting for them.  Before any pass
+ * or upload it only sets the size.  The first size change allocates the resample's destination planes
+ * (96 bytes per pixel of the maximum size).  Call it between frames, not between a frame's passes. */
+int vxpt_set_render_size(vxpt_ctx *ctx, int w, int h);
+/* the render size and the created (maximum) size; any pointer may be NULL */
+int vxpt_get_render_size(vxpt_ctx *ctx, int *w, int *h, int *max_w, int *max_h);
+/* GPU time of the last vxpt_set_render_size's resample launches (waits for them); VXPT_ERR_STATE when no
+ * call has resampled yet */
+int vxpt_render_size_ms(vxpt_ctx *ctx, float *ms);
+/* the resample's body on the host, bit for bit (no context, no GPU): src = old_w * old_h pixels of
+ * bytes_per_pixel bytes (4, 16, 20 or 32: float planes, float4 planes, reservoirs, tap records), dst =
+ * new_w * new_h pixels, not overlapping src.  VXPT_ERR_ARG for a NULL pointer, a size outside 1..32768 or
+ * another pixel size */
+int vxpt_resize_host(const void *src, int old_w, int old_h, void *dst, int new_w, int new_h, int bytes_per_pixel);
+/* The reference's controller (Backend.cpp:209-222) as a pure function: the next render width from the last
+ * frame's time.  Outside the band [1000 / (target_fps + 2), 1000 / (target_fps - 2)] ms the width is scaled
+ * by sqrtf((1000 / target_fps) / frame_ms) and truncated; then, always, it is rounded to a multiple of 16
+ * (a remainder below 8 down, 8 and above up) and clamped to [min_w, max_w]; the height is (w / 16) * 9.
+ * next_h may be NULL.  VXPT_ERR_ARG for cur_w < 1, a frame_ms or target_fps that is not positive (or NaN),
+ * min_w < 1, min_w > max_w or a NULL next_w. */
+int vxpt_dynres_next_width(int cur_w, float frame_ms, float target_fps, int min_w, int max_w, int *next_w,
+                           int *next_h);
+/* the `rendering` section of global_settings.yaml that the controller reads (GlobalSettings.cpp:433-451;
+ * defaults GlobalSettings.h:316-325 where a key or the section is absent), as of the last
+ * vxpt_load_settings.  The library only reports them: the host drives the controller */
+typedef struct vxpt_render_params {
+    float target_fps;             /* targetFPS (60) */
+    int32_t dynamic_resolution;   /* dynamicResolution (0) */
+    int32_t min_render_width, min_render_height;  /* (480, 270) */
+    int32_t max_render_width, max_render_height;  /* (2560, 1440) */
+} vxpt_render_params;
+int vxpt_get_render_params(vxpt_ctx *ctx, vxpt_render_params *out);
+/* the same section of any settings file, without a context (what vxpt_load_settings calls); VXPT_ERR_IO when
+ * the file cannot be opened */
+int vxpt_read_render_params(const char *settings_yaml, vxpt_render_params *out);
 /* OfflineBackend::writeFrameBufferToPNG (OfflineBackend.cpp:191-221): rgba = W*H float4 (the
  * frame), clamped to [0,1], x255 truncated, rows flipped, written as 8-bit RGB PNG */
 int vxpt_write_png_rgba32f(const char *path, int w, int h, const float *rgba);

@@ -317,6 +317,7 @@ int atrous_rows(int step) { return step + (step > 4 ? step / 4 : 0); }  // Atrou
 namespace vx::host {
 
 void gbuf_written(vxpt_ctx *c, int which) {
+    c->hostWrote = true;
     if (which == VXPT_BUF_MOTION) c->motionZero = false;
     if (is_gbuf_plane(which))
         for (GSlot &g : c->gb) g.recStale = true;

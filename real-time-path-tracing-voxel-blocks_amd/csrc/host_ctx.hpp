@@ -1,5 +1,5 @@
 // vxpt -- the one internal header of the host runtime (vxpt_host.cpp, host_settings.cpp, host_world.cpp, host_sky.cpp,
-// host_textures.cpp, host_instances.cpp, host_frame.cpp, host_bands.cpp, host_terrain.cpp) behind the C ABI (include/vxpt.h):
+// host_textures.cpp, host_instances.cpp, host_frame.cpp, host_bands.cpp, host_terrain.cpp, host_resize.cpp) behind the C ABI (include/vxpt.h):
 // the context, its allocation helpers, and the host functions that are called across files.
 //
 // The library is built with default visibility: everything in vx::host is declared hidden here, so
@@ -55,6 +55,9 @@ vxpt_tuning tuning_defaults();  // host_settings.cpp; exported by name like the 
 
 struct vxpt_ctx {
     int W = 0, H = 0, dev = 0, rowBegin = 0, rowEnd = 0;
+    // dynamic resolution (vxpt_set_render_size; host_resize.cpp): W x H is the render size, maxW x maxH the
+    // created one, which every per-pixel allocation is sized for
+    int maxW = 0, maxH = 0;
     int totalBounce = 3, diffuseBounce = 1;
     std::string dataDir;
     std::string err;
@@ -125,6 +128,14 @@ struct vxpt_ctx {
     MatDev mats[32] = {};  // by block id: 1..12 cubes (kernel arguments), 13..29 instanced meshes (meshMats)
     CamDev cam{}, prevCam{};
     float camYaw = 0, camPitch = 0;
+    // what the two cameras were made from (make_camera_angles' arguments): a resize makes them again at the
+    // new size.  heldW x heldH (0: none): the size the history was rendered at, set by a resize that changed
+    // the aspect ratio -- until the next frame's denoiser is enqueued the previous camera is a view of that
+    // aspect at the new resolution (the view the resampled history holds); do_denoise then makes it again
+    // at the render size (release_held_camera)
+    struct CamSrc { float pos[3] = {0.f, 0.f, 0.f}, yaw = 0.f, pitch = 0.f, fov = 90.f; bool set = false; };
+    CamSrc camSrc, prevCamSrc;
+    int heldW = 0, heldH = 0;
 
     // sky
     DBuf<float4> sky, sun;
@@ -271,6 +282,17 @@ struct vxpt_ctx {
     float4 *ffColor = nullptr;
     Reservoir *ffRes = nullptr;
     bool denoiseInputIsAccum = false;
+    // dynamic resolution: the planes outside the G-buffer ring that outlive a frame are resampled into these
+    // shadows (allocated at the first size change) and exchange pointers with them; hostWrote: a per-pixel
+    // buffer was uploaded (with no pass and no upload yet, a resize only sets the size); rzEv: around the
+    // last resample's kernels
+    float4 *shPrevIllum = nullptr, *shPrevFast = nullptr, *shMotion = nullptr;
+    float *shHistLen = nullptr, *shPrevHistLen = nullptr;
+    Reservoir *shRes = nullptr;
+    bool hostWrote = false;
+    hipEvent_t rzEv[2] = {};
+    bool rzTimed = false;
+    vxpt_render_params renderParams{60.0f, 0, 480, 270, 2560, 1440};  // GlobalSettings.h:316-325
     // Wavefront state sets, used round-robin by pass: first halves (k_closest .. the RIS
     // visibility rays) run in order on frontStream, each after the pass that last used its set;
     // second halves (temporal reuse, its rays, k_finish, later segments, the spp accumulation) run
@@ -411,6 +433,9 @@ inline const vxpt_denoise_params *denoise_or_yaml(const vxpt_ctx *c, const vxpt_
 
 // vxpt_host.cpp
 CamDev make_camera(int W, int H, const vxpt_camera &in, float *yawOut, float *pitchOut);
+CamDev make_camera_src(int W, int H, const vxpt_ctx::CamSrc &s);
+CamDev history_camera(const vxpt_ctx *c, const vxpt_ctx::CamSrc &s);
+void release_held_camera(vxpt_ctx *c);
 bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, void **mirror);
 
 // host_settings.cpp

@@ -96,6 +96,8 @@ int ensure_wave(vxpt_ctx *c, int set, size_t ns, bool &fresh) {
     fresh = false;
     if (c->wbSlots[set] >= ns) return 0;
     fresh = true;
+    // a whole-frame context allocates for the created size, so that a render size that grows back finds room
+    if (!is_banded(c)) ns = std::max(ns, (size_t)((c->maxW + 7) / 8) * ((c->maxH + 7) / 8) * 64);
     WaveBufs &w = c->wb[set];
     w = WaveBufs{};  // a smaller earlier set stays allocated (freed with the context)
     if (dalloc(c, w.pPos, ns) || dalloc(c, w.pDir, ns) || dalloc(c, w.pThr, ns) || dalloc(c, w.pRad, ns) ||
@@ -372,6 +374,7 @@ int do_denoise(vxpt_ctx *c, const vxpt_denoise_params *p, int frameNum, int it) 
     }
     HIPCHK(c, history_copies(c));
     HIPCHK(c, hipEventRecord(c->ev[3], st));
+    release_held_camera(c);  // (after a resize that changed the aspect ratio; nothing otherwise)
     return 0;
 }
 
@@ -402,7 +405,10 @@ int run_pass(vxpt_ctx *c, const vxpt_denoise_params *p, int pass, int arg, int a
             const float4 *src = arg == 1 ? a.ping : (arg == 2 ? a.pong : (arg == 3 ? a.prevIllum : a.illum));
             HIPCHK(c, launch_copy_output(a, src, c->stream));
         } break;
-        case 14: HIPCHK(c, history_copies(c)); break;
+        case 14:  // the end of a chain composed from single passes: as at the end of do_denoise
+            HIPCHK(c, history_copies(c));
+            release_held_camera(c);
+            break;
         case 15:
         case 16:
             if (is_banded(c))
@@ -501,6 +507,20 @@ int vxpt_render_frames(vxpt_ctx *c, const vxpt_denoise_params *p, int32_t frame0
     // refused before anything is enqueued: the context is left as it was
     if (const char *sw = prefilter_switch(denoise_or_yaml(c, p)))
         if (is_banded(c)) return refuse_prefilter(c, sw);
+    // the frame after a resize that changed the aspect ratio has a previous camera of its own (heldW): it
+    // runs unpipelined, since the next frame's first half is planned before this frame's denoiser
+    // (the timings are the two runs' combined: means per frame over all nFrames)
+    if (c->heldW && nFrames > 1) {
+        if (int r = vxpt_render_frames(c, p, frame0, 1, spp)) return r;
+        const vxpt_timing first = c->timing;
+        if (int r = vxpt_render_frames(c, p, frame0 + 1, nFrames - 1, spp)) return r;
+        const float rest = (float)(nFrames - 1), all = (float)nFrames;
+        c->timing.trace_ms = (first.trace_ms + c->timing.trace_ms * rest) / all;
+        c->timing.denoise_ms = (first.denoise_ms + c->timing.denoise_ms * rest) / all;
+        c->timing.frame_ms = (first.frame_ms + c->timing.frame_ms * rest) / all;
+        c->timing.host_ms = (first.host_ms + c->timing.host_ms * rest) / all;
+        return VXPT_OK;
+    }
     const auto hostT0 = std::chrono::steady_clock::now();
     auto hostMs = [&]() {
         return (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - hostT0).count() /
@@ -648,7 +668,7 @@ int vxpt_get_sun_projection(vxpt_ctx *c, float out6[6]) {
 
 // the post-process buffers, allocated on first use
 int post_alloc(vxpt_ctx *c) {
-    const size_t n = (size_t)c->W * c->H;
+    const size_t n = (size_t)c->maxW * c->maxH;  // the created size: the render size may grow back to it
     if (!c->frame) {
         if (dalloc(c, c->bloomA, n) || dalloc(c, c->bloomB, n) ||
             dalloc(c, c->frame, n) || dalloc(c, c->postHist, kPostHist) || dalloc(c, c->postState, 4))
@@ -770,7 +790,7 @@ int vxpt_debug_clamp_decisions(vxpt_ctx *c, int on) {
     HIPCHK(c, hipSetDevice(c->dev));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (on && !c->clampDbg)  // kept until the context goes (zero-filled)
-        if (int r = dalloc(c, c->clampDbg, (size_t)c->W * c->H)) return r;
+        if (int r = dalloc(c, c->clampDbg, (size_t)c->maxW * c->maxH)) return r;
     c->clampDbgOn = on != 0;
     return VXPT_OK;
 }

@@ -217,6 +217,8 @@ int vxpt_load_settings(vxpt_ctx *c) {
     }
     c->yamlDenoise = d;
     c->yamlPost = pp;
+    if (int r = vxpt_read_render_params((c->dataDir + "/settings/global_settings.yaml").c_str(), &c->renderParams))
+        return fail(c, r, "cannot read the rendering settings");
     // materials.yaml (order == material index, MaterialManager.cpp:84-97) + blocks.yaml
     std::ifstream fm(c->dataDir + "/assets/materials.yaml");
     if (!fm) return fail(c, VXPT_ERR_IO, "missing assets/materials.yaml");
@@ -298,6 +300,38 @@ int vxpt_get_denoise_params(vxpt_ctx *c, vxpt_denoise_params *out) {
 int vxpt_get_post_params(vxpt_ctx *c, vxpt_post_params *out) {
     if (!c || !out) return VXPT_ERR_ARG;
     *out = c->yamlPost;
+    return VXPT_OK;
+}
+
+int vxpt_read_render_params(const char *path, vxpt_render_params *out) {
+    if (!path || !out) return VXPT_ERR_ARG;
+    std::ifstream f(path);
+    if (!f) return VXPT_ERR_IO;
+    vxpt_render_params rp{60.0f, 0, 480, 270, 2560, 1440};  // GlobalSettings.h:316-325
+    std::string line, section;
+    while (std::getline(f, line)) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line = line.substr(0, hash);
+        if (trim(line).empty()) continue;
+        const size_t col = line.find(':');
+        if (col == std::string::npos) continue;
+        const std::string key = trim(line.substr(0, col)), val = trim(line.substr(col + 1));
+        if (line[0] != ' ' && line[0] != '\t') { section = key; continue; }
+        if (section != "rendering") continue;  // GlobalSettings.cpp:433-451: the controller's keys
+        if (key == "targetFPS") rp.target_fps = (float)std::atof(val.c_str());
+        else if (key == "dynamicResolution") rp.dynamic_resolution = as_bool(val) ? 1 : 0;
+        else if (key == "minRenderWidth") rp.min_render_width = std::atoi(val.c_str());
+        else if (key == "minRenderHeight") rp.min_render_height = std::atoi(val.c_str());
+        else if (key == "maxRenderWidth") rp.max_render_width = std::atoi(val.c_str());
+        else if (key == "maxRenderHeight") rp.max_render_height = std::atoi(val.c_str());
+    }
+    *out = rp;
+    return VXPT_OK;
+}
+
+int vxpt_get_render_params(vxpt_ctx *c, vxpt_render_params *out) {
+    if (!c || !out) return VXPT_ERR_ARG;
+    *out = c->renderParams;
     return VXPT_OK;
 }
 

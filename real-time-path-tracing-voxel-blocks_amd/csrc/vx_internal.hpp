@@ -482,6 +482,18 @@ hipError_t launch_mesh_occluded(const MeshDev &m, const float *rays, int n, unsi
 hipError_t launch_tri_lights(const float *tri, int nTri, const int *inst, int nInst, V3 radiance, LightInfo *out,
                              float *weight, hipStream_t st);
 
+// dynamic resolution (resize.hip; body in resize.hpp): planes of one record size resampled from oldW x oldH to
+// newW x newH in one launch, dst[k] from src[k] (never the same memory: a packed plane's resample overlaps
+// itself).  bytesPerPixel: 4, 16, 20 (reservoirs) or 32 (tap records)
+constexpr int kResizePlanes = 16;
+struct ResizePlanes {
+    const void *src[kResizePlanes];
+    void *dst[kResizePlanes];
+    int n;
+};
+hipError_t launch_resize(const ResizePlanes &p, int bytesPerPixel, int oldW, int oldH, int newW, int newH,
+                         hipStream_t st);
+
 hipError_t launch_firefly(const DenoiseArgs &a, int wy0, int wy1, bool detect, bool apply, hipStream_t st);
 hipError_t launch_frame0_init(const DenoiseArgs &a, hipStream_t st);
 hipError_t launch_stream_mark(hipStream_t st);

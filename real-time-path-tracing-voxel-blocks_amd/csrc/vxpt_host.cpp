@@ -75,6 +75,28 @@ CamDev make_camera(int W, int H, const vxpt_camera &in, float *yawOut, float *pi
     return make_camera_angles(W, H, in.pos, yaw, pitch, in.fov_deg);
 }
 
+CamDev make_camera_src(int W, int H, const vxpt_ctx::CamSrc &s) {
+    return make_camera_angles(W, H, s.pos, s.yaw, s.pitch, s.fov);
+}
+
+// The previous camera of pose s.  After a resize that changed the aspect ratio (heldW x heldH: the size the
+// history was rendered at) it keeps that size's view and takes the render size's resolution: the
+// reprojection then lands on the pixel of the resampled history that holds the reprojected point.
+CamDev history_camera(const vxpt_ctx *c, const vxpt_ctx::CamSrc &s) {
+    if (!c->heldW) return make_camera_src(c->W, c->H, s);
+    CamDev k = make_camera_src(c->heldW, c->heldH, s);
+    k.res = V2((float)c->W, (float)c->H);
+    k.invRes = V2(1.0f / k.res.x, 1.0f / k.res.y);
+    return k;
+}
+
+// behind the frame that reprojected into the resampled history: the previous camera at the render size
+void release_held_camera(vxpt_ctx *c) {
+    if (!c->heldW) return;
+    c->heldW = c->heldH = 0;
+    if (c->prevCamSrc.set) c->prevCam = make_camera_src(c->W, c->H, c->prevCamSrc);
+}
+
 // pointer + byte size of a logical buffer
 bool buffer_ptr(vxpt_ctx *c, int which, void *&p, size_t &bytes, bool forWrite, void **mirror) {
     const size_t n = (size_t)c->W * c->H;
@@ -164,7 +186,7 @@ int vxpt_create(const vxpt_config *cfg, vxpt_ctx **out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= cfg->device) return VXPT_ERR_NODEV;
     auto *c = new vxpt_ctx();
-    c->W = cfg->width; c->H = cfg->height; c->dev = cfg->device;
+    c->W = c->maxW = cfg->width; c->H = c->maxH = cfg->height; c->dev = cfg->device;
     c->rowBegin = cfg->row_begin; c->rowEnd = cfg->row_end;
     if (c->rowEnd <= c->rowBegin) { c->rowBegin = 0; c->rowEnd = c->H; }
     if (cfg->total_bounce_limit > 0) c->totalBounce = cfg->total_bounce_limit;
@@ -256,6 +278,8 @@ void vxpt_destroy(vxpt_ctx *c) {
     if (c->exDone) hipEventDestroy(c->exDone);
     for (hipEvent_t e : c->upEv)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->rzEv)
+        if (e) hipEventDestroy(e);
     if (c->skyWritten) hipEventDestroy(c->skyWritten);
     if (c->hSkyHeads) hipHostFree(c->hSkyHeads);
     for (hipEvent_t e : {c->worldWritten, c->editDone[0], c->editDone[1], c->wbEv[0], c->wbEv[1]})
@@ -276,14 +300,22 @@ void vxpt_destroy(vxpt_ctx *c) {
 int vxpt_set_camera(vxpt_ctx *c, const vxpt_camera *cur, const vxpt_camera *prev) {
     if (!c || !cur) return VXPT_ERR_ARG;
     c->cam = make_camera(c->W, c->H, *cur, &c->camYaw, &c->camPitch);
-    c->prevCam = make_camera(c->W, c->H, prev ? *prev : *cur, nullptr, nullptr);
+    const vxpt_camera &pv = prev ? *prev : *cur;
+    float pyaw, ppitch;
+    c->prevCam = make_camera(c->W, c->H, pv, &pyaw, &ppitch);
+    c->camSrc = {{cur->pos[0], cur->pos[1], cur->pos[2]}, c->camYaw, c->camPitch, cur->fov_deg, true};
+    c->prevCamSrc = {{pv.pos[0], pv.pos[1], pv.pos[2]}, pyaw, ppitch, pv.fov_deg, true};
+    if (c->heldW) c->prevCam = history_camera(c, c->prevCamSrc);
     return VXPT_OK;
 }
 
 int vxpt_set_camera_angles(vxpt_ctx *c, const float pos[3], float yaw, float pitch, float fovDeg) {
     if (!c || !pos) return VXPT_ERR_ARG;
     c->prevCam = c->cam;  // historyCamera = camera (mainOffline.cpp:278-279)
+    c->prevCamSrc = c->camSrc;
+    if (c->heldW && c->prevCamSrc.set) c->prevCam = history_camera(c, c->prevCamSrc);
     c->cam = make_camera_angles(c->W, c->H, pos, yaw, pitch, fovDeg);
+    c->camSrc = {{pos[0], pos[1], pos[2]}, yaw, pitch, fovDeg, true};
     c->camYaw = yaw;
     c->camPitch = pitch;
     return VXPT_OK;

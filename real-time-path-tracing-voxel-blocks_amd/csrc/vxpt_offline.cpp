@@ -13,7 +13,8 @@
 // <prefix>_frames.csv of the library's timings; --render-scale S traces and post-processes at S times
 // the output size and brings the frame up to it with vxpt_upscale (--upscale, --sharpness) before it
 // is saved: the reference's interactive back end does the same (Backend::dynamicResolution), its
-// offline one does not.  --time-of-day, --sun-axis-angle, --sun-axis-rotate and --sky-build set the sky
+// offline one does not; --render-size-schedule and --dynamic-resolution move the render size between frames
+// (vxpt_set_render_size, the histories carried over) with every saved frame scaled up.  --time-of-day, --sun-axis-angle, --sun-axis-rotate and --sky-build set the sky
 // (the reference reads it from its settings; here the defaults are its values 0.25, 45, 0).
 // The scripted voxel-edit sequences (--test-sequence, --test-remove20, --test-remove-circle) follow
 // the reference's timing: a click set after frame N is picked at frame N+1 against the world as
@@ -65,6 +66,12 @@ struct Options {
     float renderScale = 1.0f, sharpness = 1.0f;
     int upscaleMode = VXPT_UPSCALE_EASU_SHARPEN;
     int renderWidth = 0, renderHeight = 0;
+    // dynamic resolution (vxpt_set_render_size): the size set before frame F (0-based) of a schedule, or the
+    // reference's controller on each frame's measured time (targetFps 0: the settings file's)
+    struct SizeAt { int frame, w, h; };
+    std::vector<SizeAt> sizeSchedule;
+    bool dynamicResolution = false;
+    float targetFps = 0.0f;
     // the sky: time of day (a T0:T1 range moves it linearly over the frames and sets it before each),
     // the sun's axis, and where the tables are built (-1: device for a range, host otherwise)
     float tod0 = 0.25f, tod1 = 0.25f, sunAxisAngle = 45.0f, sunAxisRotate = 0.0f;
@@ -132,6 +139,14 @@ void usage(const char *argv0) {
               << "  --upscale <filter>     bicubic | easu | easu-sharp (default: easu-sharp): Catmull-Rom, the\n"
               << "                         edge-adaptive upsampler, or the upsampler and the sharpener\n"
               << "  --sharpness <f>        Strength of easu-sharp's sharpener, 0 <= f <= 1 (default: 1)\n"
+              << "  --render-size-schedule F:WxH[,F:WxH...]\n"
+              << "                         Set the render size to W x H before frame F (counted from 0), at most the\n"
+              << "                         size the run starts at; the histories are carried over.  Every saved frame\n"
+              << "                         is scaled up to --width x --height with the --upscale filter\n"
+              << "  --dynamic-resolution   Set the render size after every frame from its measured time, by the\n"
+              << "                         reference's rule (16:9 sizes, widths in multiples of 16 between the\n"
+              << "                         settings' minRenderWidth and the starting width); not deterministic\n"
+              << "  --target-fps <n>       The controller's target (default: the settings' targetFPS)\n"
               << "  --time-of-day <t>      Time of day of the sky (default: 0.25), or T0:T1: the time moves linearly\n"
               << "                         from T0 at the first frame to T1 at the last, the sky is rebuilt before\n"
               << "                         each frame, and every frame is saved\n"
@@ -199,6 +214,24 @@ int parse(int argc, char **argv, Options &o) {
             }
         }
         else if (a == "--render-scale") { if ((v = next("--render-scale"))) { o.renderScale = (float)std::atof(v); } }
+        else if (a == "--render-size-schedule") {
+            if ((v = next("--render-size-schedule"))) {
+                std::stringstream ss(v);
+                std::string item;
+                while (std::getline(ss, item, ',')) {
+                    Options::SizeAt e{};
+                    char tail = 0;
+                    if (std::sscanf(item.c_str(), "%d:%dx%d%c", &e.frame, &e.w, &e.h, &tail) != 3 || e.frame < 0 || e.w < 1 ||
+                        e.h < 1) {
+                        std::cerr << "--render-size-schedule takes F:WxH[,F:WxH...]\n";
+                        return -1;
+                    }
+                    o.sizeSchedule.push_back(e);
+                }
+            }
+        }
+        else if (a == "--dynamic-resolution") o.dynamicResolution = true;
+        else if (a == "--target-fps") { if ((v = next("--target-fps"))) { o.targetFps = (float)std::atof(v); } }
         else if (a == "--sharpness") { if ((v = next("--sharpness"))) { o.sharpness = (float)std::atof(v); } }
         else if (a == "--upscale") {
             if ((v = next("--upscale"))) {
@@ -323,6 +356,20 @@ int parse(int argc, char **argv, Options &o) {
         o.renderWidth = side(o.width);
         o.renderHeight = side(o.height);
     }
+    for (const auto &e : o.sizeSchedule)
+        if (e.w > o.renderWidth || e.h > o.renderHeight) {
+            std::cerr << "--render-size-schedule: " << e.w << "x" << e.h << " is larger than the starting size "
+                      << o.renderWidth << "x" << o.renderHeight << "\n";
+            return -1;
+        }
+    if (o.dynamicResolution && !o.sizeSchedule.empty()) {
+        std::cerr << "--dynamic-resolution and --render-size-schedule exclude each other\n";
+        return -1;
+    }
+    if (o.targetFps != 0.0f && (!o.dynamicResolution || !(o.targetFps > 2.0f))) {
+        std::cerr << "--target-fps needs --dynamic-resolution and a value above 2\n";
+        return -1;
+    }
     if (o.perfReport.empty()) o.perfReport = o.dataDir + "/perf/performance_report.txt";
     return 1;
 }
@@ -429,8 +476,11 @@ int main(int argc, char **argv) {
                                              std::to_string(o.renderWidth) + "x" + std::to_string(o.renderHeight) +
                                              " traced, " + upscale_name(o.upscaleMode) + " to the resolution)\n"
                                        : std::string())
+              << (o.dynamicResolution ? "Dynamic resolution: on, from each frame's measured time\n" : std::string())
               << "Frames to render: " << o.totalFrames << " at " << o.spp << " spp\n"
               << "Output prefix: " << o.outputPrefix << std::endl;
+    for (const auto &e : o.sizeSchedule)
+        std::cout << "Render size schedule: " << e.w << "x" << e.h << " from frame " << e.frame << std::endl;
 
     vxpt_config cfg{};
     cfg.width = o.renderWidth;
@@ -539,7 +589,16 @@ int main(int argc, char **argv) {
     std::vector<FrameRecord> perf;
     std::string runStamp;
     const size_t frameBytes = (size_t)o.width * o.height * 4 * sizeof(float);
-    const bool upscale = o.renderScale < 1.0f;
+    // a render size that moves: every saved frame is brought to the output size
+    const bool resizing = o.dynamicResolution || !o.sizeSchedule.empty();
+    const bool upscale = o.renderScale < 1.0f || resizing;
+    int curW = o.renderWidth, curH = o.renderHeight, nextW = curW, nextH = curH;
+    vxpt_render_params rp{};
+    if (vxpt_get_render_params(ctx, &rp) != VXPT_OK) return fail("reading the rendering settings");
+    const float targetFps = o.targetFps > 0.0f ? o.targetFps : rp.target_fps;
+    if (o.dynamicResolution)
+        std::cout << "Dynamic resolution: target " << targetFps << " fps, widths "
+                  << std::min(rp.min_render_width, o.renderWidth) << ".." << o.renderWidth << std::endl;
 
     for (int frame = 0; frame < o.totalFrames; frame++) {  // mainOffline.cpp:273-408
         const int frameNumber = frame + 1;
@@ -608,6 +667,15 @@ int main(int argc, char **argv) {
             if (set_sky(tod) != VXPT_OK) return fail("building the sky");
         }
 
+        for (const auto &e : o.sizeSchedule)
+            if (e.frame == frame) { nextW = e.w; nextH = e.h; }
+        if (resizing && (nextW != curW || nextH != curH)) {
+            if (vxpt_set_render_size(ctx, nextW, nextH) != VXPT_OK) return fail("setting the render size");
+            curW = nextW;
+            curH = nextH;
+            std::cout << "RENDER SIZE: frame " << frameNumber << " at " << curW << "x" << curH << std::endl;
+        }
+
         const double updateMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (vxpt_render_frame(ctx, &dp, frame, o.spp) != VXPT_OK) return fail("rendering");
         const auto tp = std::chrono::steady_clock::now();
@@ -626,11 +694,18 @@ int main(int argc, char **argv) {
         const auto t1 = std::chrono::steady_clock::now();
         FrameRecord rec{frameNumber,
                         (shouldSave ? "Saved frame " : "Convergence frame ") + std::to_string(frameNumber) + "/" +
-                            std::to_string(o.totalFrames),
+                            std::to_string(o.totalFrames) +
+                            (resizing ? " traced at " + std::to_string(curW) + "x" + std::to_string(curH) : std::string()),
                         {}, std::chrono::duration<double, std::milli>(t1 - tp).count(),
                         std::chrono::duration<double, std::milli>(t1 - t0).count(), dtMs, updateMs};
         vxpt_timings(ctx, &rec.t);
         perf.push_back(rec);
+        if (o.dynamicResolution) {  // Backend::dynamicResolution on the frame's GPU time; a 16:9 height inside the maximum
+            const int minW = std::min(std::max(rp.min_render_width, 16), o.renderWidth);
+            if (vxpt_dynres_next_width(curW, rec.t.frame_ms, targetFps, minW, o.renderWidth, &nextW, &nextH) != VXPT_OK)
+                return fail("the resolution controller");
+            nextH = std::min(std::max(nextH, 1), o.renderHeight);
+        }
         // the clicks the reference scripts after a frame (mainOffline.cpp:346-395)
         if (o.removalCircle) {
             if (circleDone < kCircleRemovals) {
@@ -672,6 +747,8 @@ int main(int argc, char **argv) {
         const std::string csv = o.outputPrefix + "_frames.csv";
         std::ofstream rep(csv);
         rep << "# " << o.runComment << "\n# " << o.width << "x" << o.height << ", " << o.spp << " spp"
+            << (resizing ? ", render size per frame in the comment column, starting"
+                         : std::string())
             << (upscale ? ", traced at " + std::to_string(o.renderWidth) + "x" + std::to_string(o.renderHeight) : std::string())
             << "\n"
             << "frame,trace_ms,denoise_ms,sky_ms,frame_ms,post_ms,wall_ms,dt_ms,comment\n";

@@ -125,6 +125,12 @@ class Timing(ctypes.Structure):
                 ("frame_ms", ctypes.c_float), ("host_ms", ctypes.c_float)]
 
 
+class RenderParams(ctypes.Structure):  # vxpt_render_params
+    _fields_ = [("target_fps", ctypes.c_float), ("dynamic_resolution", ctypes.c_int32),
+                ("min_render_width", ctypes.c_int32), ("min_render_height", ctypes.c_int32),
+                ("max_render_width", ctypes.c_int32), ("max_render_height", ctypes.c_int32)]
+
+
 class TerrainDesc(ctypes.Structure):  # vxpt_terrain_desc
     _fields_ = [("chunks", ctypes.c_int * 3), ("height_scale", ctypes.c_float), ("freq_den", ctypes.c_float),
                 ("flags", ctypes.c_int), ("origin", ctypes.c_int * 3), ("seed", ctypes.c_uint)]
@@ -245,6 +251,13 @@ def load_library(path=LIB_PATH):
         "vxpt_upscale_host": (I, [P, I, I, P, I, I, I, F]),
         "vxpt_prefilter_host": (I, [I, I, I, ctypes.POINTER(Camera), I, P, P, P, P, P, P]),
         "vxpt_upscale_info": (I, [P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(F)]),
+        "vxpt_set_render_size": (I, [P, I, I]),
+        "vxpt_get_render_size": (I, [P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)]),
+        "vxpt_render_size_ms": (I, [P, ctypes.POINTER(F)]),
+        "vxpt_resize_host": (I, [P, I, I, P, I, I, I]),
+        "vxpt_dynres_next_width": (I, [I, F, F, I, I, ctypes.POINTER(I), ctypes.POINTER(I)]),
+        "vxpt_get_render_params": (I, [P, ctypes.POINTER(RenderParams)]),
+        "vxpt_read_render_params": (I, [ctypes.c_char_p, ctypes.POINTER(RenderParams)]),
         "vxpt_get_sun_projection": (I, [P, P]),
         "vxpt_get_denoise_params": (I, [P, ctypes.POINTER(DenoiseParams)]),
         "vxpt_write_png_rgba32f": (I, [ctypes.c_char_p, I, I, P]),
@@ -699,6 +712,30 @@ class Renderer:
         self._chk(self.lib.vxpt_upscale(self.ctx, int(out_w), int(out_h), int(mode), float(sharpness)), "vxpt_upscale")
         return self.read("FRAME_UPSCALED")
 
+    def set_render_size(self, w, h):
+        """vxpt_set_render_size: the render size from the next frame on (at most the created size), the
+        histories resampled to it; read, write and upscale follow it."""
+        self._chk(self.lib.vxpt_set_render_size(self.ctx, int(w), int(h)), "vxpt_set_render_size")
+        self.W, self.H = int(w), int(h)
+
+    def render_size(self):
+        """(w, h, max_w, max_h): the render size and the created one."""
+        v = [ctypes.c_int() for _ in range(4)]
+        self._chk(self.lib.vxpt_get_render_size(self.ctx, *[ctypes.byref(x) for x in v]), "vxpt_get_render_size")
+        return tuple(x.value for x in v)
+
+    def render_size_ms(self):
+        """HIP-event milliseconds of the last set_render_size's resample launches."""
+        ms = ctypes.c_float()
+        self._chk(self.lib.vxpt_render_size_ms(self.ctx, ctypes.byref(ms)), "vxpt_render_size_ms")
+        return ms.value
+
+    def render_params(self):
+        """The `rendering` section of global_settings.yaml (load_settings), or the reference's defaults."""
+        p = RenderParams()
+        self._chk(self.lib.vxpt_get_render_params(self.ctx, ctypes.byref(p)), "vxpt_get_render_params")
+        return p
+
     def upscale_info(self):
         """(out_w, out_h, HIP-event milliseconds) of the last upscale."""
         w, h, ms = ctypes.c_int(), ctypes.c_int(), ctypes.c_float()
@@ -1135,6 +1172,40 @@ def upscale_host(image, out_w, out_h, mode=UPSCALE_EASU_SHARPEN, sharpness=1.0):
 
 
 PREFILTER_HIT_DIST, PREFILTER_PRE_PASS = 0, 1
+
+
+def resize_host(arr, new_w, new_h):
+    """vxpt_resize_host: the point resample of vxpt_set_render_size on the host.  arr is [h, w] or
+    [h, w, ...]; a pixel's bytes are its dtype's times the trailing shape (4, 16, 20 or 32)."""
+    a = np.ascontiguousarray(arr)
+    if a.ndim < 2:
+        raise VxptError("resize_host: expected an array of [h, w, ...]")
+    h, w = a.shape[:2]
+    bpp = a.dtype.itemsize * int(np.prod(a.shape[2:], dtype=np.int64))
+    out = np.zeros((int(new_h), int(new_w)) + a.shape[2:], a.dtype)
+    rc = load_library().vxpt_resize_host(_ptr(a), w, h, _ptr(out), int(new_w), int(new_h), bpp)
+    if rc != 0:
+        raise VxptError("vxpt_resize_host failed (%d): sizes 1..32768, pixels of 4, 16, 20 or 32 bytes" % rc)
+    return out
+
+
+def read_render_params(settings_yaml):
+    """vxpt_read_render_params: the `rendering` section of a settings file (no context, no GPU)."""
+    p = RenderParams()
+    rc = load_library().vxpt_read_render_params(str(settings_yaml).encode(), ctypes.byref(p))
+    if rc != 0:
+        raise VxptError("vxpt_read_render_params failed (%d): %s" % (rc, settings_yaml))
+    return p
+
+
+def dynres_next_width(cur_w, frame_ms, target_fps=60.0, min_w=480, max_w=2560):
+    """vxpt_dynres_next_width: (next_w, next_h) of the reference's controller (Backend.cpp:209-222)."""
+    w, h = ctypes.c_int(), ctypes.c_int()
+    rc = load_library().vxpt_dynres_next_width(int(cur_w), float(frame_ms), float(target_fps), int(min_w), int(max_w),
+                                               ctypes.byref(w), ctypes.byref(h))
+    if rc != 0:
+        raise VxptError("vxpt_dynres_next_width failed (%d)" % rc)
+    return w.value, h.value
 
 
 def prefilter_host(stage, illum, depth, normal_rough, material, camera, iteration_index=0, taps=False):
